@@ -19,7 +19,10 @@ no collective on the data path; barrier + max-over-ranks timing only), `n_gpus` 
   4), RCCL all-reduce of the gradient bucket + SyncBatchNorm; a step = one optimiser step.
 --config E: 500k Gaussians, SH3, 1920x1080, 9 views, forward (HBM-bound stress).
 
-Prints ONE JSON line (rank 0) with
+A plain run sets up, warms up, times the steps, writes the last timed step's outputs when --dump-outputs DIR is
+given, and prints ONE JSON line (rank 0) whose `roofline`, `cpu_baseline` and `psnr` are null.  With --full the
+line also holds
+  * `psnr`: the PSNR delta vs the oracle on one view of the benchmarked scene (eval configs, N=1);
   * `roofline` for the dominant kernel family (the fp32-accurate MFMA GEMMs): algorithmic FLOP of every GEMM
     launch of one unit of work (a refine; for C/D one training micro-step, forward + backward) / the summed
     in-context launch durations (HIP events around each launch on the launch stream, in the real sequence,
@@ -89,18 +92,28 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="scenes per step (C) / micro-steps (D)")
     ap.add_argument("--flash", action="store_true",
                     help="PointTransformerV3Model.enable_flash=True (K=1024 windows, pointtransformer_v3.py:121-123)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-psnr", action="store_true", help="skip the PSNR delta vs the oracle (eval configs)")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC passes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline probe, the rocprofv3 PMC traffic passes, the PSNR "
+                         "delta vs the oracle and the CPU baseline (a plain run times the steps and prints the line with "
+                         "those fields null)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float32; an "
+                         "array over its share of 60 MB is a fixed seeded sample of its elements, in index order)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-psnr", action="store_true", help="--full: skip the PSNR delta vs the oracle (eval configs)")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the rocprofv3 PMC passes")
     ap.add_argument("--cpu-sample", type=int, default=None,
                     help="Gaussians in the CPU-oracle sample (default: the whole scene)")
     ap.add_argument("--profile-only", action="store_true", help="skip roofline probe, traffic and CPU baseline")
     ap.add_argument("--markers", action="store_true",
                     help="launch sfx_profile_marker before every timed step and after the last (PMC passes)")
     ap.add_argument("--gemm-calls", type=str, default=None,
-                    help="write the roofline probe's per-launch list (kind, shape, ms, TF/s; median pass) to this file")
+                    help="--full: write the roofline probe's per-launch list (kind, shape, ms, TF/s; median pass) to "
+                         "this file")
     ap.add_argument("--dry-launch", action="store_true", help=argparse.SUPPRESS)  # launcher test: no GPU work
     a = ap.parse_args(argv)
+    if a.gemm_calls and not a.full:
+        ap.error("--gemm-calls lists the roofline probe's launches: it needs --full")
     dflt = DEFAULTS[a.config]
     a.n = a.n if a.n is not None else dflt[0]
     res = a.res if a.res is not None else dflt[1]
@@ -549,9 +562,34 @@ def cpu_baseline_from_psnr(psnr, n_total, views):
     }
 
 
+# ---- the last timed step's outputs (--dump-outputs) ----------------------------------------------------------
+DUMP_BUDGET_BYTES = 60_000_000  # all files together (float32 payload)
+
+
+def dump_outputs(outdir, arrays):
+    """Write each tensor of `arrays` (name -> tensor) as outdir/<name>.npy in float32 (float64 kept).  The files
+    share DUMP_BUDGET_BYTES equally: an array with more elements than its share is written as a sample of its
+    flattened elements at indices drawn once from a generator seeded with 0 (a function of the array's size and the
+    share only, so two builds given the same arguments write the same elements), in ascending index order."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))  # bytes per file
+    for name, t in arrays.items():
+        t = (torch.stack(list(t)) if isinstance(t, (list, tuple)) else t).detach()  # (per-view lists: [V, ...])
+        t = t if t.dtype == torch.float64 else t.float()
+        cap = share // t.element_size()
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(outdir, f"{name}.npy"), t.cpu().numpy())
+
+
 # ---- main -----------------------------------------------------------------------------------------------------
 def main(argv=None):
     args = parse(argv)
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if needs_launch(args.gpus):  # before anything touches the GPU
         sys.exit(subprocess.call(launch_cmd(args.gpus, sys.argv[1:] if argv is None else argv, _free_port())))
     from splatformer_amd import dist as sdist
@@ -587,7 +625,7 @@ def main(argv=None):
         def step():
             out = model([scene], [rank])[0]
             rgbs, alphas = rasterize_gaussians_to_multiimgs(out, cams)
-            return rgbs
+            return {**{f"refined_{k}": v for k, v in out.items()}, "rgbs": rgbs, "alphas": alphas}
 
         def unit():  # the GEMM family's unit of work: one refine
             model.refine_packed(scene)
@@ -604,15 +642,20 @@ def main(argv=None):
         tr = Trainer(model, accumulate_step=(n_sc if args.config == "D" else 1), group=group,
                      generator=torch.Generator(device=dev).manual_seed(rank), precision=args.train_prec)
 
+        def trained(losses):  # what a training step leaves its caller: the losses, the gradient norm, the weights
+            return {"loss": torch.tensor(losses, dtype=torch.float64), "grad_norm": tr.last_norm,
+                    "params": torch.cat([p.detach().reshape(-1) for p in tr.params])}
+
         if args.config == "C":
             def step():
-                tr.micro_step(scenes, [cams] * n_sc, gts)
+                loss = tr.micro_step(scenes, [cams] * n_sc, gts)
                 tr.optimizer_step()
+                return [loss]
         else:
             def step():
-                for i in range(n_sc):
-                    tr.micro_step([scenes[i]], [cams], [gts[i]])
+                losses = [tr.micro_step([scenes[i]], [cams], [gts[i]]) for i in range(n_sc)]
                 tr.optimizer_step()
+                return losses
 
         def unit():  # one training micro-step of one scene: train forward + backward (no optimiser step)
             tr.micro_step([scenes[0]], [cams], [gts[0]])
@@ -625,9 +668,13 @@ def main(argv=None):
     sdist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
         marker(i)
-        step()
+        res = step()
+        if i == args.steps - 1:  # only the last step's result outlives its step
+            last = res
+        del res
     marker(args.steps)
     torch.cuda.synchronize()
     sdist.barrier()
@@ -639,9 +686,13 @@ def main(argv=None):
     if not train:
         model.check_refine()
     _lib.check_lookback("bench.py timed steps")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trained(last) if train else last)
+    del last
 
+    full = args.full and not args.profile_only
     roof = None
-    if not args.profile_only:
+    if full:
         if not train:
             model.eval()
         roof = roofline_probe(unit, dump=args.gemm_calls if rank == 0 else None)
@@ -655,11 +706,11 @@ def main(argv=None):
             else:
                 roof["traffic_note"] = err
     psnr = None
-    if rank == 0 and world == 1 and not train and not args.no_psnr and not args.profile_only:
+    if rank == 0 and world == 1 and not train and not args.no_psnr and full:
         psnr = psnr_delta(model, scene, scene_cpu, cams, cams_cpu, sd_cpu, bk, args.sh)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_only:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and full:
         # the whole scene by default (no extrapolation in N); --cpu-sample bounds it for quick runs
         sample = min(args.cpu_sample or args.n, args.n)
         if train:

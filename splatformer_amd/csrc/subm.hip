@@ -185,10 +185,10 @@ __global__ void __launch_bounds__(256) subm_pair_write_kernel(int n, const int* 
   for (int k = 0; k < 27; ++k) {
     int base = first[(long long)k * nb + blockIdx.x];
     for (int w = 0; w < wid; ++w) base += wc[k][w];
-    const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(bal[k] >> 32),
-                                                    __builtin_amdgcn_mbcnt_lo((unsigned)bal[k], 0u));
+    const unsigned lrank = __builtin_amdgcn_mbcnt_hi((unsigned)(bal[k] >> 32),
+                                                     __builtin_amdgcn_mbcnt_lo((unsigned)bal[k], 0u));
     const bool fl = (bal[k] >> lane) & 1ull;
-    const int p = base + (int)rank;
+    const int p = base + (int)lrank;
     if (fl) {
       pair_out[p] = i;
       pair_in[p] = row[k];

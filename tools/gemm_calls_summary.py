@@ -1,4 +1,4 @@
-"""Aggregate bench.py --gemm-calls output by (kind, shape): calls, total ms, TF/s.
+"""Aggregate bench.py --full --gemm-calls output by (kind, shape): calls, total ms, TF/s.
 usage: python tools/gemm_calls_summary.py <file.jsonl> [top]"""
 import collections
 import json
