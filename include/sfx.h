@@ -498,6 +498,22 @@ int sfx_rasterize_bwd_quad(int tiles_x, int tiles_y, int block_width, int img_h,
                            const float* opacity, const float* background, const float* final_Ts, const int* final_idx,
                            const float* v_out, const float* v_out_alpha, float* v_xy, float* v_xy_abs, float* v_conic,
                            float* v_rgb, float* v_opacity, void* stream);
+/* (ABI v16, additive) gsplat rasterize_forward / rasterize_backward for any channel count 1 <= channels <= 32
+ * (depth maps, normals, feature vectors): colors [N,channels], background [channels], out_img and v_out
+ * [H,W,channels], v_colors [N,channels]; everything else as sfx_rasterize_fwd / sfx_rasterize_bwd, over gsplat's
+ * list or a culled one (the same list for both calls), block_width 2..16.  The backward accumulates (+=) into
+ * v_xy, v_xy_abs, v_conic, v_colors and v_opacity with float atomics: zero them first; more than 32 channels are
+ * rendered in slabs over the same list (final_Ts / final_idx do not depend on the colours), passing v_out_alpha
+ * with one slab only.  out_alpha, v_out_alpha and v_xy_abs may be NULL. */
+int sfx_rasterize_fwd_nd(int tiles_x, int tiles_y, int block_width, int img_h, int img_w, int channels,
+                         const int32_t* gids_sorted, const int* tile_bins, const float* xys, const float* conics,
+                         const float* colors, const float* opacity, const float* background, float* final_Ts,
+                         int* final_idx, float* out_img, float* out_alpha, void* stream);
+int sfx_rasterize_bwd_nd(int tiles_x, int tiles_y, int block_width, int img_h, int img_w, int channels,
+                         const int32_t* gids_sorted, const int* tile_bins, const float* xys, const float* conics,
+                         const float* colors, const float* opacity, const float* background, const float* final_Ts,
+                         const int* final_idx, const float* v_out, const float* v_out_alpha, float* v_xy,
+                         float* v_xy_abs, float* v_conic, float* v_colors, float* v_opacity, void* stream);
 
 /* ---- evaluation post-processing ------------------------------------------------------------------
  * Replaces train.py:104-113 `(x*255).to(torch.uint8)` of prediction (after the gs_utils.py:111

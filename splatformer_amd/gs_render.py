@@ -121,7 +121,55 @@ def _rowptr(t: Tensor, width: int):
     return t2.data_ptr(), t2.stride(0), t2
 
 
-def _render_fused(gs, c2w, cx, cy, fx, fy, W, H, background):
+def rasterize_gaussians_to_rgbd(gs_params, camera_to_world, cx, cy, fx, fy, width, height, background_color,
+                                depth_mode="accumulated", **kwargs):
+    """rasterize_gaussians_to_singleimg plus a depth map -> (rgb [H,W,3] clamped <= 1, alpha [H,W,1], depth
+    [H,W,1]), from ONE 4-channel pass over colours [rgb | z] (z: the camera-space depth of the projection) on
+    background [background_color | 0].  depth_mode "accumulated": sum_i w_i z_i; "expected": that over alpha where
+    alpha > 0, 0 elsewhere.  With grad the depth gradient reaches the means through the projection backward."""
+    if depth_mode not in ("accumulated", "expected"):
+        raise ValueError(f"depth_mode must be 'accumulated' or 'expected', got {depth_mode!r}")
+    gs_params = {k: v.float() if v.dtype == torch.half else v for k, v in gs_params.items()}
+    if "opacities" not in gs_params and "opacities_sigmoid" not in gs_params:
+        raise ValueError("No opacities found in gs_params")
+    H, W = int(_scalar(height)), int(_scalar(width))
+    fx, fy, cx, cy = _scalar(fx), _scalar(fy), _scalar(cx), _scalar(cy)
+    if _needs_grad(gs_params) or "opacities_sigmoid" in gs_params:
+        rgb, alpha, depth = _render_autograd(gs_params, camera_to_world, cx, cy, fx, fy, W, H, background_color,
+                                             depth=True)
+    else:
+        rgb, alpha, depth = _render_fused(gs_params, camera_to_world, cx, cy, fx, fy, W, H, background_color,
+                                          depth=True)
+    if depth_mode == "expected":
+        depth = torch.where(alpha > 0, depth / alpha.clamp_min(torch.finfo(torch.float32).tiny),
+                            torch.zeros_like(depth))
+    return rgb, alpha, depth
+
+
+def rasterize_gaussians_to_multirgbd(gs_params: Dict[str, Tensor], cameras: Dict, depth_mode: str = "accumulated"
+                                     ) -> Tuple[List[Tensor], List[Tensor], List[Tensor]]:
+    """rasterize_gaussians_to_rgbd for every camera_to_world of `cameras`, view by view (the batched-views pass of
+    rasterize_gaussians_to_multiimgs is 3-channel) -> (rgbs, alphas, depths)."""
+    rgbs, alphas, depths = [], [], []
+    for camera_to_world in cameras["camera_to_worlds"]:
+        rgb, alpha, depth = rasterize_gaussians_to_rgbd(gs_params, camera_to_world, depth_mode=depth_mode, **cameras)
+        rgbs.append(rgb)
+        alphas.append(alpha)
+        depths.append(depth)
+    return rgbs, alphas, depths
+
+
+def _with_depth(rgbs, depths, background):
+    """Colours [rgb | z] and background [background | 0] of the 4-channel RGB-D pass."""
+    bg = background.to(device=rgbs.device, dtype=torch.float32)
+    return torch.cat([rgbs, depths[:, None]], 1), torch.cat([bg, bg.new_zeros(1)])
+
+
+def _split_depth(out, alpha):
+    return torch.clamp(out[..., :3], max=1.0), alpha.unsqueeze(-1), out[..., 3:4]
+
+
+def _render_fused(gs, c2w, cx, cy, fx, fy, W, H, background, depth=False):
     means = gs["means"]
     _lib.require_gpu(means)
     dev = means.device
@@ -144,6 +192,10 @@ def _render_fused(gs, c2w, cx, cy, fx, fy, W, H, background):
     call("sfx_render_prep_project", n, nb, pm, lm, ps, ls, pq, lq, po, lo, pd, ldc, pr, lr, ptr(c2w), fx, fy, cx, cy,
          H, W, BLOCK_WIDTH, ptr(viewmat), ptr(rgbs), ptr(opac), ptr(xys), ptr(depths), ptr(radii), ptr(conics),
          ptr(tiles), stream())
+    if depth:
+        colors, bg = _with_depth(rgbs, depths, background)
+        return _split_depth(*rasterize_gaussians(xys, depths, radii, conics, tiles, colors, opac, H, W, BLOCK_WIDTH,
+                                                 background=bg, return_alpha=True))
     bg = background.to(device=dev, dtype=torch.float32).contiguous()
     rgb, alpha = _RasterizeGaussians.apply(xys, depths, radii, conics, tiles, rgbs, opac, H, W, BLOCK_WIDTH, bg, True)
     rgb = torch.clamp(rgb, max=1.0)
@@ -309,7 +361,8 @@ def _autograd_views(means, c2ws):
     return viewmats, vd
 
 
-def _render_autograd(gs_params, camera_to_world, cx, cy, fx, fy, W, H, background_color, prep=None, view=None):
+def _render_autograd(gs_params, camera_to_world, cx, cy, fx, fy, W, H, background_color, prep=None, view=None,
+                     depth=False):
     """Line-for-line the reference glue (gs_utils.py:32-112) over the HIP autograd ops (`prep`: _autograd_prep of
     the same Gaussians, shared by the views of a scene; `view`: this view's (viewmat, view directions) from
     _autograd_views)."""
@@ -326,6 +379,10 @@ def _render_autograd(gs_params, camera_to_world, cx, cy, fx, fy, W, H, backgroun
         rgbs = torch.clamp(rgbs + 0.5, min=0.0)
     xys, depths, radii, conics, comp, num_tiles_hit, cov3d = project_gaussians(
         means, scales, 1, quats, viewmat, fx, fy, cx, cy, H, W, BLOCK_WIDTH)
+    if depth:
+        colors, bg = _with_depth(rgbs, depths, background_color)
+        return _split_depth(*rasterize_gaussians(xys, depths, radii, conics, num_tiles_hit, colors, opacities, H, W,
+                                                 BLOCK_WIDTH, background=bg, return_alpha=True))
     rgb, alpha = rasterize_gaussians(xys, depths, radii, conics, num_tiles_hit, rgbs, opacities, H, W, BLOCK_WIDTH,
                                      background=background_color, return_alpha=True)
     rgb = torch.clamp(rgb, max=1.0)
@@ -333,5 +390,6 @@ def _render_autograd(gs_params, camera_to_world, cx, cy, fx, fy, W, H, backgroun
     return rgb, alpha
 
 
-__all__ = ["rasterize_gaussians_to_multiimgs", "rasterize_gaussians_to_singleimg", "render_views_meta", "BLOCK_WIDTH", "SH2RGB", "RGB2SH",
+__all__ = ["rasterize_gaussians_to_multiimgs", "rasterize_gaussians_to_singleimg", "rasterize_gaussians_to_rgbd",
+           "rasterize_gaussians_to_multirgbd", "render_views_meta", "BLOCK_WIDTH", "SH2RGB", "RGB2SH",
            "bin_and_sort_gaussians", "compute_cumulative_intersects"]

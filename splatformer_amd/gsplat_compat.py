@@ -43,6 +43,8 @@ _lib.register("sfx_pack_raster_records", [_I, _P, _P, _P, _P, _P, _P])
 _lib.register("sfx_rasterize_fwd_views_quad", [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P])
 _lib.register("sfx_rasterize_bwd_quad", [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                          _P, _P, _P])
+_lib.register("sfx_rasterize_fwd_nd", [_I] * 6 + [_P] * 12)
+_lib.register("sfx_rasterize_bwd_nd", [_I] * 6 + [_P] * 17)
 
 
 def _f32(t: Tensor) -> Tensor:
@@ -253,20 +255,11 @@ def _culled_counts(n, num_tiles_hit, xys, radii, conics, opacity, H, W, tiles_x,
     return nonempty, total, cum
 
 
-def _culled_forward(n, xys, depths, radii, conics, colors, opacity, background, H, W, tiles_x, tiles_y, total, cum):
-    """The forward over the culled list (single view): culled emission over the surviving tile counts' scan (from
-    _culled_counts) -> the same stable sort and bins -> rasterize_fwd_views_quad.  Called when gsplat's own list is
-    non-empty."""
+def _culled_list(n, xys, depths, radii, conics, opacity, H, W, tiles_x, tiles_y, total, cum):
+    """(gids_sorted, tile_bins) of the culled list (single view, total >= 1): culled emission over the surviving
+    tile counts' scan (from _culled_counts) -> the same stable sort and bins as gsplat's list."""
     dev = xys.device
     num_tiles = tiles_x * tiles_y
-    final_Ts = torch.empty(H, W, device=dev, dtype=torch.float32)
-    final_idx = torch.empty(H, W, device=dev, dtype=torch.int32)
-    if total < 1:  # nothing reaches 1/255 anywhere: T = 1 at every pixel (gsplat's normal path, alpha 0)
-        out = background.reshape(1, 1, -1).expand(H, W, background.shape[0]).contiguous()
-        final_Ts.fill_(1.0)
-        final_idx.zero_()
-        return (out, torch.zeros(H, W, device=dev), final_Ts, final_idx,
-                torch.zeros(0, device=dev, dtype=torch.int32), torch.zeros(num_tiles, 2, device=dev, dtype=torch.int32))
     isect = torch.empty(total, device=dev, dtype=torch.int64)
     gids = torch.empty(total, device=dev, dtype=torch.int32)
     call("sfx_isect_emit_cull_views", n, n, ptr(xys), ptr(conics), ptr(opacity), ptr(depths), ptr(radii), ptr(cum),
@@ -277,6 +270,27 @@ def _culled_forward(n, xys, depths, radii, conics, colors, opacity, background, 
          32 + max(1, int(num_tiles - 1).bit_length()), ptr(ws), ws.numel(), stream())
     tile_bins = torch.empty(num_tiles, 2, device=dev, dtype=torch.int32)
     call("sfx_tile_bins", total, ptr(isect_s), num_tiles, ptr(tile_bins), stream())
+    return gids_s, tile_bins
+
+
+def _all_culled(background, H, W, tiles_x, tiles_y):
+    """Nothing reaches 1/255 anywhere: T = 1 at every pixel (gsplat's normal path, alpha 0) and empty lists."""
+    dev = background.device
+    out = background.reshape(1, 1, -1).expand(H, W, background.shape[0]).contiguous()
+    return (out, torch.zeros(H, W, device=dev), torch.ones(H, W, device=dev),
+            torch.zeros(H, W, device=dev, dtype=torch.int32), torch.zeros(0, device=dev, dtype=torch.int32),
+            torch.zeros(tiles_x * tiles_y, 2, device=dev, dtype=torch.int32))
+
+
+def _culled_forward(n, xys, depths, radii, conics, colors, opacity, background, H, W, tiles_x, tiles_y, total, cum):
+    """The forward over the culled list (single view): _culled_list -> rasterize_fwd_views_quad.  Called when
+    gsplat's own list is non-empty."""
+    dev = xys.device
+    if total < 1:
+        return _all_culled(background, H, W, tiles_x, tiles_y)
+    gids_s, tile_bins = _culled_list(n, xys, depths, radii, conics, opacity, H, W, tiles_x, tiles_y, total, cum)
+    final_Ts = torch.empty(H, W, device=dev, dtype=torch.float32)
+    final_idx = torch.empty(H, W, device=dev, dtype=torch.int32)
     rec = torch.empty(n, 16, device=dev, dtype=torch.float32)
     call("sfx_pack_raster_records", n, ptr(xys), ptr(conics), ptr(colors), ptr(opacity), ptr(rec), stream())
     out = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
@@ -286,15 +300,108 @@ def _culled_forward(n, xys, depths, radii, conics, colors, opacity, background, 
     return out, alpha, final_Ts, final_idx, gids_s, tile_bins
 
 
+_ND_SLAB = 32  # channels per launch of the N-channel kernels (their largest tier)
+
+
+class _RasterizeGaussiansND(torch.autograd.Function):
+    """_RasterizeGaussians for any channel count, over sfx_rasterize_fwd_nd / sfx_rasterize_bwd_nd: the same list
+    choice (culled when CULL, block_width 16 and n > 0), the same empty-list quirk, the same return contract.
+    More than 32 channels: slabs of at most 32 over ONE sorted list -- compositing is linear per channel and the
+    geometry does not depend on the colours, so every slab ends with the same final_Ts / final_idx."""
+
+    @staticmethod
+    def forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height, img_width,
+                block_width, background, return_alpha):
+        _lib.require_gpu(xys)
+        dev = xys.device
+        n, C = xys.shape[0], colors.shape[-1]
+        H, W, bw = int(img_height), int(img_width), int(block_width)
+        tiles_x, tiles_y = (W + bw - 1) // bw, (H + bw - 1) // bw
+        xys, conics, colors, opacity, background = map(_f32, (xys, conics, colors, opacity, background))
+        radii = radii.to(torch.int32).contiguous()
+        culled = CULL and bw == 16 and n > 0
+        if culled:
+            num_isect, kept_total, kept_cum = _culled_counts(n, num_tiles_hit, xys, radii, conics, opacity, H, W,
+                                                             tiles_x, tiles_y)
+        else:
+            num_isect, cum = compute_cumulative_intersects(num_tiles_hit) if n else (0, None)
+        ctx.num_isect = num_isect
+        if num_isect < 1:
+            out = torch.ones(H, W, C, device=dev) * background
+            gids_sorted = torch.zeros(0, device=dev, dtype=torch.int32)
+            tile_bins = torch.zeros(0, 2, device=dev, dtype=torch.int32)
+            final_Ts = torch.zeros(H, W, device=dev)  # gsplat v0.1.11 empty-branch quirk (alpha == 1)
+            final_idx = torch.zeros(H, W, device=dev, dtype=torch.int32)
+            alpha = 1 - final_Ts
+        elif culled and kept_total < 1:
+            out, alpha, final_Ts, final_idx, gids_sorted, tile_bins = _all_culled(background, H, W, tiles_x, tiles_y)
+        else:
+            if culled:
+                gids_sorted, tile_bins = _culled_list(n, xys, _f32(depths), radii, conics, opacity, H, W, tiles_x,
+                                                      tiles_y, kept_total, kept_cum)
+            else:
+                _, _, _, gids_sorted, tile_bins = bin_and_sort_gaussians(n, num_isect, xys, _f32(depths), radii, cum,
+                                                                         (tiles_x, tiles_y, 1), bw)
+            out = torch.empty(H, W, C, device=dev, dtype=torch.float32)
+            final_Ts = torch.empty(H, W, device=dev, dtype=torch.float32)
+            final_idx = torch.empty(H, W, device=dev, dtype=torch.int32)
+            alpha = torch.empty(H, W, device=dev, dtype=torch.float32)
+            for s in range(0, C, _ND_SLAB):
+                e = min(s + _ND_SLAB, C)
+                whole = e - s == C
+                col = colors if whole else colors[:, s:e].contiguous()
+                o = out if whole else torch.empty(H, W, e - s, device=dev, dtype=torch.float32)
+                call("sfx_rasterize_fwd_nd", tiles_x, tiles_y, bw, H, W, e - s, ptr(gids_sorted), ptr(tile_bins),
+                     ptr(xys), ptr(conics), ptr(col), ptr(opacity), ptr(background[s:e]), ptr(final_Ts),
+                     ptr(final_idx), ptr(o), ptr(alpha) if s == 0 else None, stream())
+                if not whole:
+                    out[..., s:e] = o
+        ctx.img = (H, W, bw, tiles_x, tiles_y)
+        ctx.save_for_backward(gids_sorted, tile_bins, xys, conics, colors, opacity, background, final_Ts, final_idx)
+        if return_alpha:
+            return out, alpha
+        return out
+
+    @staticmethod
+    def backward(ctx, v_out_img, v_out_alpha=None):
+        gids_sorted, tile_bins, xys, conics, colors, opacity, background, final_Ts, final_idx = ctx.saved_tensors
+        H, W, bw, tiles_x, tiles_y = ctx.img
+        dev = xys.device
+        n, C = xys.shape[0], colors.shape[-1]
+        v_xy = torch.zeros(n, 2, device=dev)
+        v_conic = torch.zeros(n, 3, device=dev)
+        v_colors = torch.zeros(n, C, device=dev)
+        v_op = torch.zeros_like(opacity)
+        if ctx.num_isect >= 1:
+            v_out_img = _f32(v_out_img)
+            v_out_alpha = _f32(v_out_alpha) if v_out_alpha is not None else None
+            v_xy_abs = torch.zeros(n, 2, device=dev)
+            # an empty culled list (nothing reaches 1/255): no pixel depends on any input
+            for s in range(0, C, _ND_SLAB) if gids_sorted.numel() else ():
+                e = min(s + _ND_SLAB, C)
+                whole = e - s == C
+                col = colors if whole else colors[:, s:e].contiguous()
+                vo = v_out_img if whole else v_out_img[..., s:e].contiguous()
+                vc = v_colors if whole else torch.zeros(n, e - s, device=dev)
+                # the geometry gradients accumulate across the slabs; v_out_alpha enters once
+                call("sfx_rasterize_bwd_nd", tiles_x, tiles_y, bw, H, W, e - s, ptr(gids_sorted), ptr(tile_bins),
+                     ptr(xys), ptr(conics), ptr(col), ptr(opacity), ptr(background[s:e]), ptr(final_Ts),
+                     ptr(final_idx), ptr(vo), ptr(v_out_alpha) if s == 0 else None, ptr(v_xy), ptr(v_xy_abs),
+                     ptr(v_conic), ptr(vc), ptr(v_op), stream())
+                if not whole:
+                    v_colors[:, s:e] = vc
+            xys.absgrad = v_xy_abs
+        return (v_xy, None, None, v_conic, None, v_colors, v_op) + (None,) * 5
+
+
 def rasterize_gaussians(xys: Tensor, depths: Tensor, radii: Tensor, conics: Tensor, num_tiles_hit: Tensor,
                         colors: Tensor, opacity: Tensor, img_height: int, img_width: int, block_width: int,
                         background: Optional[Tensor] = None, return_alpha: Optional[bool] = False):
-    """Front-to-back tile rasterizer (3-channel), gsplat v0.1.11 contract: out_img [H,W,3] (+ alpha [H,W])."""
+    """Front-to-back tile rasterizer, gsplat v0.1.11 contract: out_img [H,W,C] (+ alpha [H,W]) for colors [N,C].
+    C == 3 runs the 3-channel kernels; any other C >= 1 (depth, normals, feature vectors) the N-channel ones."""
     assert block_width > 1 and block_width <= 16, "block_width must be between 2 and 16"
     if colors.dtype == torch.uint8:
         colors = colors.float() / 255
-    if colors.shape[-1] != 3:
-        raise NotImplementedError("only the 3-channel rasterizer is on the SplatFormer path")
     if background is not None:
         assert background.shape[0] == colors.shape[-1], \
             f"incorrect shape of background color tensor, expected shape {colors.shape[-1]}"
@@ -304,6 +411,9 @@ def rasterize_gaussians(xys: Tensor, depths: Tensor, radii: Tensor, conics: Tens
         raise ValueError("xys must have dimensions (N, 2)")
     if colors.ndimension() != 2:
         raise ValueError("colors must have dimensions (N, D)")
-    return _RasterizeGaussians.apply(xys.contiguous(), depths.contiguous(), radii.contiguous(), conics.contiguous(),
-                                     num_tiles_hit.contiguous(), colors.contiguous(), opacity.contiguous(),
-                                     img_height, img_width, block_width, background.contiguous(), return_alpha)
+    if colors.shape[-1] < 1:
+        raise ValueError("colors must have at least one channel")
+    fn = _RasterizeGaussians if colors.shape[-1] == 3 else _RasterizeGaussiansND
+    return fn.apply(xys.contiguous(), depths.contiguous(), radii.contiguous(), conics.contiguous(),
+                    num_tiles_hit.contiguous(), colors.contiguous(), opacity.contiguous(), img_height, img_width,
+                    block_width, background.contiguous(), return_alpha)
