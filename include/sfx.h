@@ -586,12 +586,22 @@ int sfx_block_mlp_bwd(int M, int C, const float* dy, long long lddy, const float
  *   (row o, column k C + i: spconv [Cout, 3, 3, 3, Cin]) -> wpk (sfx_subm_cpe_pack_bytes(C) bytes of fp16x2
  *   fragments) + winv [C] (inverse column scales); ws: C floats.
  * sfx_subm_cpe_ln: xc = the conv input, xres = the shortcut (they differ for the first Block after an
- *   unpooling: Pointcept's stale sparse_conv_feat), nbr [n][27] (sfx_subm_neighbors), bias = the folded b'. */
+ *   unpooling: Pointcept's stale sparse_conv_feat), nbr [n][27] (sfx_subm_neighbors), bias = the folded b';
+ *   perm [n] = the order the kernel walks the map's rows in (a permutation of 0..n-1: the argsort of
+ *     sfx_subm_order_keys on bits [0, 16), built once per map);
+ *   rowexp [n] = sfx_subm_rowexp(xc), the per-row fp16x2 exponents of the conv input.
+ * sfx_subm_order_keys: keys[i] = a 16-bit key of row i's neighbour mask (which of 16 chosen offsets of nbr [n][27]
+ *   are present); an argsort of bits [0, 16) groups rows of like neighbourhoods (the perm above).
+ * sfx_subm_rowexp: e[i] = the exponent with max |x[i][:]| * 2^e[i] in [2^14, 2^15) (127 for an all-zero row);
+ *   x [n][C] contiguous, 16-byte aligned, C a multiple of 4 (sfx_block_mlp's rowexp output holds the same values). */
 size_t sfx_subm_cpe_pack_bytes(int C);
 int sfx_subm_cpe_pack(int C, const float* w, void* wpk, float* winv, float* ws, void* stream);
-int sfx_subm_cpe_ln(int n, int C, const float* xc, const float* xres, const int* nbr, const void* wpk,
-                    const float* winv, const float* bias, const float* gamma_cpe, const float* beta_cpe,
-                    const float* gamma1, const float* beta1, float eps, float* x_out, float* h_out, void* stream);
+int sfx_subm_order_keys(int n, const int* nbr, uint64_t* keys, void* stream);
+int sfx_subm_rowexp(int n, int C, const float* x, int* e, void* stream);
+int sfx_subm_cpe_ln(int n, int C, const float* xc, const float* xres, const int* nbr, const int* perm,
+                    const int* rowexp, const void* wpk, const float* winv, const float* bias, const float* gamma_cpe,
+                    const float* beta_cpe, const float* gamma1, const float* beta1, float eps, float* x_out,
+                    float* h_out, void* stream);
 
 /* (ABI v11) PTv3 embedding (reference pointtransformer_v3.py:273-278: Linear(Cin, C) -> BatchNorm1d eval ->
  * GELU) on the VALU for Cin <= 64, C in {32, 64}: y[i] = GELU((x[i] W^T + b) * scale + shift); x rows strided

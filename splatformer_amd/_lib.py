@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
 
 import torch
@@ -16,56 +17,55 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFX_LIB", os.path.join(_HERE, "libsfx.so"))
 
-P = C.c_void_p
-I = C.c_int
-L = C.c_longlong
-F = C.c_float
-Z = C.c_size_t
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "sfx.h")
 
-# name -> argtypes (restype int unless listed in _RESTYPES)
-SIGNATURES: dict[str, list] = {
-    "sfx_abi_version": [],
-    "sfx_last_error": [],
-    "sfx_scan_workspace_bytes": [L],
-    "sfx_lookback_timeouts": [P],
-    "sfx_lookback_release": [P],
-    "sfx_scan_i32": [L, P, P, I, P, Z, P, P],
-    "sfx_scan_i64": [L, P, P, I, P, Z, P, P],
-    "sfx_sort_workspace_bytes": [L],
-    "sfx_sort_pairs_u64": [L, P, P, P, P, I, I, P, Z, P],
-    "sfx_sh_fwd": [I, I, I, P, P, P, P],
-    "sfx_sh_bwd": [I, I, I, P, P, P, P],
-    "sfx_project_fwd": [I, P, P, F, P, P, F, F, F, F, I, I, I, F, P, P, P, P, P, P, P, P],
-    "sfx_project_bwd": [I, P, P, F, P, P, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
-    "sfx_render_prep_project": [I, I, P, L, P, L, P, L, P, L, P, L, P, L, P, F, F, F, F, I, I, I, P, P, P, P, P, P, P,
-                                P, P],
-    "sfx_isect_emit": [I, P, P, P, P, I, I, I, P, P, P],
-    "sfx_tile_bins": [I, P, I, P, P],
-    "sfx_profile_marker": [I, P],
-    "sfx_rasterize_fwd": [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P],
-    "sfx_rasterize_bwd": [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
+_SCALARS = {
+    "int": C.c_int, "unsigned": C.c_uint, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong,
+    "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "int32_t": C.c_int32, "int64_t": C.c_int64,
+    "uint64_t": C.c_uint64,
 }
-_RESTYPES = {
-    "sfx_abi_version": C.c_int,
-    "sfx_last_error": C.c_char_p,
-    "sfx_scan_workspace_bytes": C.c_size_t,
-    "sfx_lookback_timeouts": C.c_longlong,
-    "sfx_sort_workspace_bytes": C.c_size_t,
-}
+_RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "long long": C.c_longlong, "const char*": C.c_char_p}
+_TYPE_WORDS = {w for t in _SCALARS for w in t.split()}
+_PROTO = re.compile(r"([A-Za-z_][\w\s*]*?)\b(sfx_\w+)\s*\(([^(){};]*)\)\s*;")
+
+
+def parse_header(text: str) -> tuple[dict[str, list], dict[str, type]]:
+    """(name -> argtypes, name -> restype) of every `<ret> sfx_name(<params>);` prototype of a C header text.  A
+    pointer parameter is a c_void_p (callers pass data_ptr() integers and None); scalar and return types come from
+    the fixed tables above.  Strict: a type outside the tables, or an `sfx_name(` that is not part of a prototype
+    of that form, raises and names the function -- a wrong guess would corrupt arguments silently."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    sigs, rets = {}, {}
+    for ret, name, params in _PROTO.findall(text):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RETURNS:
+            raise ValueError(f"{name}: return type '{ret}' is not one the binding knows")
+        args = []
+        for prm in ([] if params.strip() == "void" else params.split(",")):
+            words = re.sub(r"\bconst\b", " ", prm).split()
+            ctype = " ".join(words if words and words[-1] in _TYPE_WORDS else words[:-1])  # drop the parameter's name
+            if "*" not in prm and ctype not in _SCALARS:
+                raise ValueError(f"{name}: parameter '{' '.join(prm.split())}' has no known scalar type")
+            args.append(C.c_void_p if "*" in prm else _SCALARS[ctype])
+        sigs[name], rets[name] = args, _RETURNS[ret]
+    stray = re.search(r"\b(sfx_\w+)\s*\(", _PROTO.sub(" ", text))
+    if stray:
+        raise ValueError(f"{stray.group(1)}: not a `<ret> sfx_name(<params>);` prototype the binding can read")
+    return sigs, rets
+
+
+# name -> argtypes / restype of every entry point, read once from the header the library is compiled against
+with open(HEADER) as _f:
+    SIGNATURES, _RESTYPES = parse_header(_f.read())
 
 _lib = None
 _lock = threading.Lock()
 
 
-def register(name: str, argtypes: list, restype=C.c_int) -> None:
-    """Extend the signature table (used by modules that add entry points)."""
-    SIGNATURES[name] = argtypes
-    if restype is not C.c_int:
-        _RESTYPES[name] = restype
-
-
 def load(path: str | None = None):
-    """Load libsfx.so (no GPU needed); raises if it is absent."""
+    """Load libsfx.so (no GPU needed) and bind every entry point include/sfx.h declares; raises if the library is
+    absent or lacks one."""
     global _lib
     with _lock:
         if _lib is not None:
@@ -77,9 +77,13 @@ def load(path: str | None = None):
                 "(the HIP extension is required: there is no CPU fallback)")
         lib = C.CDLL(p)
         for name, args in SIGNATURES.items():
-            fn = getattr(lib, name)
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise RuntimeError(f"{p} does not export {name}, which include/sfx.h declares: the library is stale, "
+                                   "rebuild it with `python -m splatformer_amd.build_lib`") from None
             fn.argtypes = args
-            fn.restype = _RESTYPES.get(name, C.c_int)
+            fn.restype = _RESTYPES[name]
         _lib = lib
         return lib
 
@@ -89,12 +93,7 @@ def lib():
 
 
 def fn(name: str):
-    l = lib()
-    f = getattr(l, name)
-    if f.argtypes is None and name in SIGNATURES:
-        f.argtypes = SIGNATURES[name]
-        f.restype = _RESTYPES.get(name, C.c_int)
-    return f
+    return getattr(lib(), name)
 
 
 _FNS: dict = {}  # name -> resolved ctypes function (one dict lookup per launch instead of lib() + getattr + checks)

@@ -26,8 +26,6 @@
 
 #include "common.h"
 
-extern "C" int sfx_get_precision(void);  // gemm.hip (include/sfx.h)
-
 #ifndef SFX_ATTN_OCC16
 #define SFX_ATTN_OCC16 4  // workgroups per CU the d = 16 split kernel is compiled for
 #endif

@@ -11,10 +11,7 @@
 #include <cstdio>
 #include <cstdarg>
 
-#define SFX_OK 0
-#define SFX_ERR_INVALID -1
-#define SFX_ERR_HIP -2
-#define SFX_ERR_WORKSPACE -3
+#include "sfx.h"
 
 namespace sfx {
 

@@ -201,7 +201,11 @@ namespace {
 __global__ void profile_marker_kernel(int) {}
 }  // namespace
 
-extern "C" int sfx_profile_marker(int tag, void* stream) {
+extern "C" {
+
+int sfx_profile_marker(int tag, void* stream) {
   profile_marker_kernel<<<1, 1, 0, sfx::as_stream(stream)>>>(tag);
   return sfx::check_launch("sfx_profile_marker");
 }
+
+}  // extern "C"

@@ -37,8 +37,6 @@
 
 #include "gemm_common.h"
 
-extern "C" int sfx_get_precision(void);  // gemm.hip (include/sfx.h)
-
 #ifndef SFX_MLP_RING256
 #define SFX_MLP_RING256 8  // LDS ring phases of the C = 256 kernel
 #endif

@@ -214,10 +214,6 @@ __global__ void __launch_bounds__(256) subm_pair_write_kernel(int n, const int* 
 }
 }  // namespace
 
-extern "C" int sfx_scan_i32(long long n, const int32_t* in, int32_t* out, int inclusive, void* ws, size_t ws_bytes,
-                            int32_t* total, void* stream);
-extern "C" size_t sfx_scan_workspace_bytes(long long n);
-
 extern "C" {
 
 int sfx_subm_table_log2(int n) {

@@ -25,11 +25,7 @@ from torch import Tensor
 
 from . import _lib
 from . import ptv3_ops as ops
-from ._lib import I, L, P, F, call, ptr, stream
-
-_lib.register("sfx_voxel_keys", [I, P, L, F, P, P])
-_lib.register("sfx_nn1", [I, I, P, P, P, P])
-_lib.register("sfx_fps", [I, I, P, I, P, P, P])
+from ._lib import call, ptr, stream
 
 
 def _xyz(t: Tensor) -> Tensor:

@@ -21,7 +21,7 @@ from torch import Tensor
 
 from . import _lib
 from . import ptv3_ops as ops
-from ._lib import F, I, L, P, call, ptr, stream
+from ._lib import call, ptr, stream
 from .gsplat_compat import (_RasterizeGaussians, bin_and_sort_gaussians, compute_cumulative_intersects,
                             project_gaussians, rasterize_gaussians, spherical_harmonics)
 
@@ -47,19 +47,6 @@ def RGB2SH(rgb):
 
 def _scalar(x) -> float:
     return float(x.item()) if isinstance(x, Tensor) else float(x)
-
-
-_lib.register("sfx_render_prep_project_views", [I, I, I, P, L, P, L, P, L, P, L, P, L, P, L, P, F, F, F, F, I, I, I,
-                                                 P, P, P, P, P, P, P, P, P])
-_lib.register("sfx_isect_emit_views", [I, I, P, P, P, P, I, I, I, P, P, L, P])
-_lib.register("sfx_rasterize_fwd_views", [I, I, I, I, I, I, P, P, P, P, P, P, P, I, P, P, P, P, P])
-_lib.register("sfx_pack_raster_records", [I, P, P, P, P, P, P])
-_lib.register("sfx_rasterize_fwd_views_packed", [I, I, I, I, I, I, P, P, P, P, I, P, P, P, P, P])
-_lib.register("sfx_isect_count_cull_views", [I, I, P, P, P, P, I, I, I, I, I, P, P])
-_lib.register("sfx_isect_emit_cull_views", [I, I, P, P, P, P, P, P, I, I, I, I, I, P, P, P, L, P])
-_lib.register("sfx_depth_keys", [L, P, P, P])
-_lib.register("sfx_invert_permutation", [L, P, P, P])
-_lib.register("sfx_rasterize_fwd_views_quad", [I, I, I, I, I, I, P, P, P, P, I, P, P, P, P, P])
 
 
 def rasterize_gaussians_to_multiimgs(gs_params: Dict[str, Tensor], cameras: Dict) -> Tuple[List[Tensor], List[Tensor]]:

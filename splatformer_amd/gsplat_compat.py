@@ -36,15 +36,6 @@ def deg_from_sh(num_bases: int) -> int:
 # can reach alpha >= 1/255 -- forward outputs bit-identical, gradients the same sums in another atomic order.
 # SFX_RENDER_CULL=0 restores gsplat's full 3-sigma lists.
 CULL = os.environ.get("SFX_RENDER_CULL", "1") != "0"
-_I, _P = _lib.I, _lib.P
-_lib.register("sfx_isect_count_cull_views", [_I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P])
-_lib.register("sfx_isect_emit_cull_views", [_I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _lib.L, _P])
-_lib.register("sfx_pack_raster_records", [_I, _P, _P, _P, _P, _P, _P])
-_lib.register("sfx_rasterize_fwd_views_quad", [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P])
-_lib.register("sfx_rasterize_bwd_quad", [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                         _P, _P, _P])
-_lib.register("sfx_rasterize_fwd_nd", [_I] * 6 + [_P] * 12)
-_lib.register("sfx_rasterize_bwd_nd", [_I] * 6 + [_P] * 17)
 
 
 def _f32(t: Tensor) -> Tensor:

@@ -19,11 +19,7 @@ import torch
 import math
 
 from . import _lib
-from ._lib import I, L, P, Z, call, ptr, stream
-
-_lib.register("sfx_image_stats_u8", [I, L, P, P, I, P, P, P])
-_lib.register("sfx_ssim_workspace_bytes", [I, I, I, I], Z)
-_lib.register("sfx_ssim", [I, I, I, I, P, P, P, I, P, P, Z, P])
+from ._lib import call, ptr, stream
 
 
 def image_stats_u8(pred: torch.Tensor, gt: torch.Tensor, clamp_pred: bool = True):

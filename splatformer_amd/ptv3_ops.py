@@ -16,64 +16,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import I, L, P, F, Z, call, ptr, stream
-
-_lib.register("sfx_linear", [I, I, I, P, L, P, I, P, L, P, P, P, I, I, P, L, P, P, L, P, L, I, L, L, L, L, P, P, I,
-                              P, I, P, I, P, I, P, P, P])
-_lib.register("sfx_weight_split", [I, I, P, L, P, P, P])
-_lib.register("sfx_amax_f32", [I, I, P, L, P, I, P])
-_lib.register("sfx_ln_amax_bound", [I, P, P, P, I, P])
-_lib.register("sfx_layernorm", [I, I, P, L, P, P, F, P, L, P])
-_lib.register("sfx_cpe_residual_ln", [I, I, P, P, P, P, P, P, F, P, P, P])
-_lib.register("sfx_cpe_residual_ln_pairs", [I, I, P, L, P, P, L, P, P, P, P, P, F, P, P, P])
-_lib.register("sfx_cpe_ln_qkv_pairs", [I, I, P, L, P, P, L, P, P, P, P, P, F, P, P, P, P, P, P, I, P])
-_lib.register("sfx_window_attention", [I, I, I, I, I, P, P, P, F, P, P, I, P])
-_lib.register("sfx_window_attention_varlen", [I, I, I, I, I, P, P, P, F, P, P, I, P])
-_lib.register("sfx_window_attention_proj", [I, I, I, I, I, P, P, P, F, P, I, P, P, P, P, L, P, L, P])
-_lib.register("sfx_serialize_keys", [I, P, P, I, I, I, I, I, I, I, P, P, P])
-_lib.register("sfx_serialize_finalize", [I, I, P, P, P, P])
-_lib.register("sfx_serialize_permute", [I, I, P, P, P, P, P, P, P, P, P, P, P])
-_lib.register("sfx_pool_run_flags", [I, I, P, P, I, P, P])
-_lib.register("sfx_pool_run_counts", [I, P, P, P, I, P, P])
-_lib.register("sfx_pool_assign_runs", [I, I, I, P, P, P, P, P, P, P, P])
-_lib.register("sfx_pool_reorder", [I, I, I, P, P, P, P, P, P, P])
-_lib.register("sfx_pool_gather", [I, I, I, P, P, I, P, P, I, P, P, P, P, P])
-_lib.register("sfx_segment_max_affine_act", [I, I, P, P, P, P, P, I, P, P])
-_lib.register("sfx_segment_mean", [I, I, P, P, P, P, P])
-_lib.register("sfx_subm_table_log2", [I])
-_lib.register("sfx_subm_neighbors", [I, P, P, I, P, P, P, P, P, P])
-_lib.register("sfx_subm_permute", [I, P, P, P, P, P, P])
-_lib.register("sfx_subm_pairs_workspace_bytes", [I], Z)
-_lib.register("sfx_subm_pairs", [I, P, P, Z, P, P, P, I, P])
-_lib.register("sfx_subm_conv", [I, I, I, P, L, P, P, P, P, P, P, P, L, P, I, P, I, P, P, P])
-_lib.register("sfx_subm_conv_partials", [I, I, I, P, L, P, P, P, P, P, P, P, L, P, L, P, P, P])
-_lib.register("sfx_subm_conv_partials_pairs", [I, I, I, P, L, P, P, P, P, P, P, P, L, P, L, P, P, P])
-_lib.register("sfx_subm_pair_pos", [I, L, P, P, P, P])
-_lib.register("sfx_subm_pair_lists_workspace_bytes", [I], Z)
-_lib.register("sfx_subm_pair_lists", [I, P, P, Z, P, P, P, P, P, I, P])
-_lib.register("sfx_cpe_residual_ln_cpairs", [I, I, P, L, P, P, L, P, P, P, P, P, F, P, P, P])
-_lib.register("sfx_subm_cpe_pack_bytes", [I], Z)
-_lib.register("sfx_subm_cpe_pack", [I, P, P, P, P, P])
-_lib.register("sfx_subm_cpe_ln", [I, I, P, P, P, P, P, P, P, P, P, P, P, P, F, P, P, P])
-_lib.register("sfx_subm_order_keys", [I, P, P, P])
-_lib.register("sfx_subm_rowexp", [I, I, P, P, P])
-_lib.register("sfx_gs_pack", [I, P, L, P, L, P, L, P, L, P, L, P, L, I, F, P, L, P, P, P])
-_lib.register("sfx_offsets_to_batch", [I, I, P, P, P])
-_lib.register("sfx_move_rows", [L, I, P, L, P, P, L, I, P])
-_lib.register("sfx_point_embed", [I, I, I, P, L, P, P, P, P, P, L, P])
-_lib.register("sfx_heads_stream_floats", [I, I], Z)
-_lib.register("sfx_heads_params_floats", [I], Z)
-_lib.register("sfx_heads_pack", [I, I, I, P, I, P, P, P, P, P, P, P, P, P])
-_lib.register("sfx_heads", [I, I, I, I, P, L, I, I, P, P, P, P, P])
-_lib.register("sfx_gemm_force_config", [I, I])
-_lib.register("sfx_set_precision", [I])
-_lib.register("sfx_get_precision", [])
-_lib.register("sfx_mlp_stream_floats", [I], Z)
-_lib.register("sfx_mlp_params_floats", [I], Z)
-_lib.register("sfx_mlp_pack", [I, P, P, P, P, P, P, P, P, P, P])
-_lib.register("sfx_block_mlp", [I, I, P, L, P, P, F, P, L, P, P])
-_lib.register("sfx_block_mlp_train", [I, I, P, L, P, P, F, P, P, P, L, P])
-_lib.register("sfx_block_mlp_bwd", [I, I, P, L, P, P, P, P, P, L, P])
+from ._lib import call, ptr, stream
 
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
 # gemm.hip kCfgs: 128x128, 128x96, 128x64, 64x128, 64x64 (4 waves, 2 per CU), 256x128, 128x256 (8 waves)

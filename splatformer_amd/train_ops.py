@@ -6,7 +6,6 @@ Same rules as ptv3_ops: torch allocates, HIP computes, no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Optional, Tuple
 
@@ -14,33 +13,8 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import F, I, L, P, Z, call, ptr, stream
+from ._lib import call, ptr, stream
 from .ptv3_ops import _rows, weight_split
-
-D = C.c_double
-
-_lib.register("sfx_linear_bwd_data", [I, I, I, P, L, P, L, P, I, I, P, L, P, L, I, P, P, P])
-_lib.register("sfx_linear_wgrad", [I, I, I, P, L, P, L, P, L, P, P])
-_lib.register("sfx_transpose", [I, I, P, L, P, L, P])
-_lib.register("sfx_subm_conv_bwd_data", [I, I, I, P, L, P, P, P, P, P, P, P, L, P, P, P])
-_lib.register("sfx_window_attention_bwd", [I, I, I, I, I, P, P, P, F, P, P, P, P, P])
-_lib.register("sfx_window_attention_varlen_bwd", [I, I, I, I, I, P, P, P, F, P, P, P, P])
-_lib.register("sfx_layernorm_bwd", [I, I, P, L, P, P, L, P, L, F, P, L, P])
-_lib.register("sfx_cpe_ln_bwd", [I, I, P, P, P, P, P, P, F, P, P, P])
-_lib.register("sfx_colsum2_workspace_bytes", [I, I], Z)
-_lib.register("sfx_bn_stats", [I, I, P, L, P, Z, P, P])
-_lib.register("sfx_bn_finalize", [I, D, P, P, P, F, F, P, P, P, P, P, P, P])
-_lib.register("sfx_affine_act", [I, I, P, L, P, P, I, P, L, P, P, L, P])
-_lib.register("sfx_bn_act_bwd_reduce", [I, I, P, L, P, P, P, P, I, P, L, P, Z, P, P])
-_lib.register("sfx_bn_act_bwd_apply", [I, I, P, L, P, P, P, P, I, P, L, P, D, P, L, I, P])
-_lib.register("sfx_segment_max_arg", [I, I, P, P, P, P, P, P])
-_lib.register("sfx_segment_max_bwd", [I, I, P, P, P, P])
-_lib.register("sfx_segment_sum", [I, I, P, P, P, L, P, P])
-_lib.register("sfx_act_bwd", [I, I, P, L, P, L, I, I, P, L, P])
-_lib.register("sfx_sumsq", [L, P, P, P])
-_lib.register("sfx_clip_coef", [P, F, P, P, P])
-_lib.register("sfx_adam_step", [L, P, P, P, P, P, F, F, F, F, F, I, P])
-_lib.register("sfx_drop_mask", [L, F, C.c_ulonglong, P, P])
 
 DACT_NONE, DACT_GELU, DACT_RELU, DACT_TANH_OUT = 0, 1, 2, 3
 _ATTN_EXACT = os.environ.get("SFX_ATTN_PREC", "")[:1] == "f"  # (read once, as attention.hip does)
