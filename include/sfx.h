@@ -132,9 +132,14 @@ int sfx_rasterize_fwd_views_packed(int views, int tiles_x, int tiles_y, int bloc
 /* ---- refiner: Pointcept PTv3 m1 + FeaturePredictor (models/pointtransformer_v3.py, feature_predictor.py) -- */
 /* fp32 MFMA GEMM, Y = act((A' W^T + bias) * scale + shift) + R[ridx]; A' = A or, with gather_idx [M][S],
  * the concatenation of S gathered rows (SubMConv3d implicit GEMM).  act: 0 none, 1 GELU(erf), 2 ReLU,
- * 3 tanh, applied to columns < act_ncols (-1 = all).  Ypre (optional) receives the pre-residual value.
+ * 3 tanh, applied to columns < act_ncols (-1 = all).  rowscale (optional, the DropPath keep mask / keep)
+ * multiplies a row's act(.) before the residual is added: Y = rowscale * act(z) + R[ridx], z = (A' W^T + bias) *
+ * scale + shift.  Ypre (optional) receives z when pre_before_act != 0, otherwise the pre-residual value
+ * rowscale * act(z) (after the activation and rowscale, before the residual).
  * groups > 1 runs a grouped GEMM (block-diagonal heads) with the given per-group element strides.
- * out_row_idx[m] (optional) maps GEMM row m to its output row (residual_idx is indexed by output row).
+ * out_row_idx[m] (optional) maps GEMM row m to its output row, -1 drops the row; output rows that no GEMM row
+ * names are not written.  rowscale, residual_idx and the rows of Ypre are indexed by output row (R without
+ * residual_idx too).
  * Every operand must span < 2 GiB (raw buffer descriptors; out-of-range lanes read 0 / drop stores).
  * Replaces nn.Linear / BatchNorm1d(eval) / GELU / residual adds of Block, Embedding, SerializedPooling,
  * SerializedUnpooling and the FeaturePredictor heads (feature_predictor.py:74-94, :201-235), and
@@ -162,7 +167,9 @@ int sfx_weight_split(int rows, int cols, const float* w, long long ld, float* w_
  * select the other forms).  A slot is 64 unsigned long long sub-slots, zero-initialised by the caller once,
  * holding (tag << 32 | float bits) written with atomicMax; readers use the sub-slots carrying their tag.
  * a_amax / w_amax (may be NULL: the library then runs its own maxima pass) bound |A'| and |W| of a GEMM;
- * y_amax (may be NULL) receives max |Y| of a launch's outputs under y_tag (Stream-K is then not used).
+ * y_amax (may be NULL) receives an upper bound of max |Y| of a launch's outputs under y_tag (Stream-K is then not
+ * used): max |Y| itself, except that the padding rows of a ragged last row tile (rows >= M) may contribute
+ * act(bias * scale + shift), so the bound never exceeds max(max |Y|, max |act(bias * scale + shift)|).
  * sfx_amax_f32 writes max |X| of a [rows x cols] (row stride ld) matrix; sfx_ln_amax_bound writes the bound
  * sqrt(C-1) * max|gamma| + max|beta| of any LayerNorm output with those affine parameters. */
 int sfx_amax_f32(int rows, int cols, const float* x, long long ld, unsigned long long* slot, unsigned tag,
