@@ -182,6 +182,14 @@ int sfx_ln_amax_bound(int C, const float* gamma, const float* beta, unsigned lon
  * process.  Eight-wave configurations apply only to split (K >= 64) launches. */
 int sfx_gemm_force_config(int cfg, int stream_k);
 
+/* Test hook: epilogue class of every later GEMM launch of the process.  -1 (default) automatic: fp16x2 launches
+ * whose epilogue is bias / scale+shift / dense residual / y_amax with no activation or GELU, and pair launches that
+ * store per-pair rows, run a specialised straight-line epilogue; 0: every launch runs the general epilogue.  Both
+ * give bitwise equal results.  sfx_gemm_last_epilogue: the class the process's latest sfx_linear / sfx_subm_conv*
+ * launch ran (0 general, 1 linear, 2 linear + GELU, 3 pair store; -1 before the first launch). */
+int sfx_gemm_force_epilogue(int cls);
+int sfx_gemm_last_epilogue(void);
+
 /* Library operand-precision mode for every later GEMM launch issued by the calling host thread (ABI 14; per thread
  * since ABI 15 -- launches from other threads keep their own mode, default 0):
  *   0 (default) fp32-accurate: fp16x2 / bf16x3 split operands, three resp. six term products per block;

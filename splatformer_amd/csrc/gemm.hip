@@ -309,9 +309,25 @@ int pick_cfg(GemmArgs& a, int groups, bool vec) {
   return best;
 }
 
+// Epilogue class of a launch (after pick_cfg: Stream-K pieces stay general).  The specialised classes exist for
+// fp16x2 operands only; SFX_GEMM_EPI=0 or sfx_gemm_force_epilogue(0) keep every launch on EPI_GENERAL.
+int forced_epi = -2;
+int last_epi = -1;  // class of the process's latest launch (sfx_gemm_last_epilogue: tests check what ran)
+int pick_epi(const GemmArgs& a, bool vec) {
+  if (forced_epi == -2) {
+    const char* e = getenv("SFX_GEMM_EPI");
+    forced_epi = (e && *e && atoi(e) == 0) ? 0 : -1;
+  }
+  if (forced_epi == 0 || !vec || a.split != 2 || a.sk) return EPI_GENERAL;
+  if (a.pair_mode) return a.pair_store ? EPI_PAIR_STORE : EPI_GENERAL;
+  if (a.gidx || a.out_rows || a.ridx || a.Ypre || a.rowscale || a.dact) return EPI_GENERAL;
+  return a.act == ACT_NONE ? EPI_LIN : (a.act == ACT_GELU ? EPI_LIN_GELU : EPI_GENERAL);
+}
+
 template <int MODE>
 void dispatch_mode(GemmArgs a, int groups, bool vec, hipStream_t st) {
   const int cfg = pick_cfg(a, groups, vec);
+  a.epi = last_epi = pick_epi(a, vec);
   const bool w8 = kCfgs[cfg].nw == 8;
   switch (MODE) {
     case MODE_DENSE: (w8 ? launch_m0_w8 : launch_m0_w4)(cfg, a, groups, vec, st); break;
@@ -329,6 +345,7 @@ void dispatch(const GemmArgs& a0, int groups, bool vec, hipStream_t st) {
   // range-safe bf16x3 form.
   if (a.split == 2 && !a.Wsp) a.split = 3;
   if (a.split == 2 && g_prec == 1) a.split = 1;  // reference-precision mode: single fp16 term
+  last_epi = EPI_GENERAL;  // (dispatch_mode sets the class it picks)
   if (a.pair_mode)
     dispatch_mode<MODE_PAIR>(a, groups, vec, st);
   else if (!a.gidx)
@@ -607,6 +624,14 @@ int sfx_gemm_force_config(int cfg, int stream_k) {
   forced_sk = stream_k;
   return SFX_OK;
 }
+
+int sfx_gemm_force_epilogue(int cls) {
+  SFX_REQUIRE(cls == -1 || cls == 0, "sfx_gemm_force_epilogue: class %d (-1 automatic, 0 general)", cls);
+  forced_epi = cls;
+  return SFX_OK;
+}
+
+int sfx_gemm_last_epilogue(void) { return last_epi; }
 
 int sfx_weight_split(int rows, int cols, const float* w, long long ld, float* w_split, float* w_inv, void* stream) {
   SFX_REQUIRE(rows >= 0 && cols > 0 && cols % 4 == 0 && ld >= cols && ld % 4 == 0,

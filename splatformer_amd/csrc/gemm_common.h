@@ -30,6 +30,10 @@ constexpr unsigned OOB = 0x7ffffff0u;        // byte offset past every descripto
 constexpr int RSRC_FLAGS = 0x00020000;       // gfx950 raw buffer, 32-bit data
 
 enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2, ACT_TANH = 3 };
+// Epilogue classes of gemm_kernel (compile-time; gemm.hip pick_epi chooses per launch, fp16x2 operands only):
+// GENERAL every option; LIN direct rows + bias / scale+shift / dense residual / y_amax, no activation; LIN_GELU the
+// same with GELU; PAIR_STORE pair mode storing one row per pair.
+enum Epi { EPI_GENERAL = 0, EPI_LIN = 1, EPI_LIN_GELU = 2, EPI_PAIR_STORE = 3 };
 
 struct GemmArgs {
   int M, N, K;         // K = S * Kseg when gathering
@@ -97,6 +101,7 @@ struct GemmArgs {
   long long slice_winv_stride;  // pair mode: winv offset per slice (row-sliced weights, e.g. the conv backward)
   int tuned, tuned_sk;  // measured tile configuration + 1 (0: cost model / table) and its Stream-K flag
   int pair_store;  // pair mode: store each pair's row at row `pair index` of Y instead of adding into pair_out
+  int epi;         // epilogue class of the launch (Epi), set in dispatch
   // timing ablations only (SFX_GEMM_DEBUG, results wrong): bit 0 no MFMAs, 1 no operand loads (out-of-range
   // offsets), 2 no epilogue, 3 no LDS staging (split + writes)
   int dbg;

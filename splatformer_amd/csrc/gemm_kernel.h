@@ -68,9 +68,17 @@ using namespace sfxg;
 // waves rescale that row's accumulators before adding it.  The epilogue unscales each row by its final 1/s.
 // Error: that of fp32 arithmetic (dropped l*l <= 2^-22 relative, products exact in fp32) for every row,
 // whatever the other rows' magnitudes.
-template <int BM, int BN, int WGM, int NW, bool VEC, int MODE, int SPL>
+//
+// EPI = epilogue class (gemm_common.h Epi), chosen per launch by the host (gemm.hip pick_epi).  EPI_GENERAL serves
+// every option with wave-uniform runtime branches; the other classes are straight-line bodies for the epilogues the
+// eval forward runs most (fp16x2 operands only): all of a tile's loads ahead of its stores, all stores back to back,
+// the same arithmetic in the same order as the general direct epilogue (bitwise equal results).
+template <int BM, int BN, int WGM, int NW, bool VEC, int MODE, int SPL, int EPI = EPI_GENERAL>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_kernel(GemmArgs p, int tiles_n, int total_tiles) {
   constexpr bool SPLIT = SPL != 0;
+  static_assert(EPI == EPI_GENERAL || (SPL == 2 && VEC), "specialised epilogues: fp16x2 operands only");
+  static_assert((EPI != EPI_LIN && EPI != EPI_LIN_GELU) || MODE == MODE_DENSE, "EPI_LIN*: dense rows");
+  static_assert(EPI != EPI_PAIR_STORE || MODE == MODE_PAIR, "EPI_PAIR_STORE: pair mode");
   constexpr bool F16 = SPL == 2 || SPL == 1;   // fp16 terms (SPL 1: the leading term only)
   constexpr int NTERM = SPL == 1 ? 1 : (F16 ? 2 : 3);  // LDS term images per operand
   static_assert(SPL == 0 || SPL == 1 || SPL == 2 || SPL == 3, "operand precision");
@@ -494,9 +502,9 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_kernel(GemmArgs
     }
   };
 
-  auto epilogue = [&](const Tile& ti, bool partial, bool owner0) {
-    if (p.dbg & 4) return;
-    if constexpr (F16) {  // undo the row scales of A' and W (powers of two: exact)
+  // fp16x2: undo the row scales of A' and W (powers of two: exact)
+  auto unscale = [&]() {
+    if constexpr (F16) {
 #pragma unroll
       for (int a = 0; a < MB; ++a)
 #pragma unroll
@@ -510,6 +518,85 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_kernel(GemmArgs
             acc[a][b][4 * gq + 3] *= f.w * ewinv[b];
           }
         }
+    }
+  };
+
+  // EPI_LIN / EPI_LIN_GELU: direct rows, bias, optional scale/shift, optional dense residual, optional y_amax.
+  // The finished values replace the accumulators block by block while the residual rows of the next 32x32 block
+  // load; then every store of the tile is issued in one run.  An absent residual reads through a zero-extent
+  // descriptor and is selected away (v + 0 would turn -0 into +0).
+  auto lin_epilogue = [&](const Tile& ti) {
+    const unsigned Mu = (unsigned)ti.M;
+    const __amdgpu_buffer_rsrc_t rYd = rsrc_ext(Y, Mu * ldy32 * 4u);
+    const __amdgpu_buffer_rsrc_t rRd = rsrc_ext(p.R ? p.R : Y, Mu * ldr32 * 4u);
+    const bool has_r = p.R != nullptr;
+    auto load_r = [&](int blk, float (&rv)[16]) {
+      const unsigned mb = (unsigned)(ti.m0 + wm * WM + (blk / NB) * 32 + 4 * h);
+      const int n = ti.n0 + wn * WN + (blk % NB) * 32 + l32;
+      const unsigned br = n < p.N ? (mb * ldr32 + (unsigned)n) * 4u : OOBX;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) rv[r] = bload1(rRd, br + rowc(r) * ldr32 * 4u);
+    };
+    float rv[2][16];
+    load_r(0, rv[0]);
+#pragma unroll
+    for (int blk = 0; blk < MB * NB; ++blk) {
+      const int a = blk / NB, b = blk % NB;
+      if (blk + 1 < MB * NB) load_r(blk + 1, rv[(blk + 1) & 1]);
+      const bool do_act = ti.n0 + wn * WN + b * 32 + l32 < p.act_ncols;
+      const float c1 = p.scale ? escale[b] : 1.f;
+      const float c0 = ebias[b] * c1 + eshift[b];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float v = __builtin_fmaf(acc[a][b][r], c1, c0);
+        if constexpr (EPI == EPI_LIN_GELU) v = do_act ? gelu_erf(v) : v;
+        v = has_r ? v + rv[blk & 1][r] : v;
+        ymax = fmaxf(ymax, fabsf(v));
+        acc[a][b][r] = v;
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // the stores in one run, behind every load of the tile
+#pragma unroll
+    for (int a = 0; a < MB; ++a) {
+      const unsigned mb = (unsigned)(ti.m0 + wm * WM + a * 32 + 4 * h);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const int n = ti.n0 + wn * WN + b * 32 + l32;
+        const unsigned by = n < p.N ? (mb * ldy32 + (unsigned)n) * 4u : OOBX;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bstore1(rYd, by + rowc(r) * ldy32 * 4u, acc[a][b][r]);
+      }
+    }
+  };
+
+  // EPI_PAIR_STORE: row mt of the slice is row pbase + mt of the partials matrix -- direct addressing, no index
+  // loads; rows past the slice's pairs fall outside the extent (they are the next slice's rows) and are dropped.
+  auto pair_store_epilogue = [&](const Tile& ti) {
+    const unsigned pbase = (unsigned)(ti.out_rows - p.pair_out);
+    const __amdgpu_buffer_rsrc_t rYd = rsrc_ext(Y, (pbase + (unsigned)ti.M) * ldy32 * 4u);
+#pragma unroll
+    for (int a = 0; a < MB; ++a) {
+      const unsigned mb = pbase + (unsigned)(ti.m0 + wm * WM + a * 32 + 4 * h);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const int n = ti.n0 + wn * WN + b * 32 + l32;
+        const unsigned by = n < p.N ? (mb * ldy32 + (unsigned)n) * 4u : OOBX;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bstore1(rYd, by + rowc(r) * ldy32 * 4u, acc[a][b][r]);
+      }
+    }
+  };
+
+  auto epilogue = [&](const Tile& ti, bool partial, bool owner0) {
+    if (p.dbg & 4) return;
+    unscale();
+    if constexpr (EPI == EPI_LIN || EPI == EPI_LIN_GELU) {
+      lin_epilogue(ti);
+      return;
+    }
+    if constexpr (EPI == EPI_PAIR_STORE) {
+      pair_store_epilogue(ti);
+      return;
     }
     if constexpr (MODE != MODE_PAIR) {
       if (!ti.out_rows) {
@@ -832,6 +919,29 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_kernel(GemmArgs
     sfx::publish_amax(ymax, p.y_amax, p.y_tag, ywaves);
   }
 }
+// fp16x2 launch: the epilogue class the host chose (GemmArgs::epi), where this operand mode has it
+template <int BM, int BN, int WGM, int NW, int MODE>
+void launch_f16x2(const GemmArgs& a, dim3 grid, int tiles_n, int total, hipStream_t st) {
+  constexpr int T = NW * 64;
+  if constexpr (MODE == MODE_DENSE) {
+    if (a.epi == EPI_LIN) {
+      gemm_kernel<BM, BN, WGM, NW, true, MODE, 2, EPI_LIN><<<grid, T, 0, st>>>(a, tiles_n, total);
+      return;
+    }
+    if (a.epi == EPI_LIN_GELU) {
+      gemm_kernel<BM, BN, WGM, NW, true, MODE, 2, EPI_LIN_GELU><<<grid, T, 0, st>>>(a, tiles_n, total);
+      return;
+    }
+  }
+  if constexpr (MODE == MODE_PAIR) {
+    if (a.epi == EPI_PAIR_STORE) {
+      gemm_kernel<BM, BN, WGM, NW, true, MODE, 2, EPI_PAIR_STORE><<<grid, T, 0, st>>>(a, tiles_n, total);
+      return;
+    }
+  }
+  gemm_kernel<BM, BN, WGM, NW, true, MODE, 2><<<grid, T, 0, st>>>(a, tiles_n, total);
+}
+
 template <int BM, int BN, int WGM, int NW, int MODE>
 void launch(GemmArgs a, int groups, bool vec, hipStream_t st) {
   const bool split = a.split != 0;
@@ -858,14 +968,14 @@ void launch(GemmArgs a, int groups, bool vec, hipStream_t st) {
   dim3 grid(grid_x, 1, groups);
   if constexpr (NW == 8) {  // split-only tiles (vec operands)
     if (a.split == 2)
-      gemm_kernel<BM, BN, WGM, 8, true, MODE, 2><<<grid, 512, 0, st>>>(a, tiles_n, total);
+      launch_f16x2<BM, BN, WGM, 8, MODE>(a, grid, tiles_n, total, st);
     else if (a.split == 1)
       gemm_kernel<BM, BN, WGM, 8, true, MODE, 1><<<grid, 512, 0, st>>>(a, tiles_n, total);
     else
       gemm_kernel<BM, BN, WGM, 8, true, MODE, 3><<<grid, 512, 0, st>>>(a, tiles_n, total);
   } else {
     if (vec && a.split == 2)
-      gemm_kernel<BM, BN, WGM, 4, true, MODE, 2><<<grid, 256, 0, st>>>(a, tiles_n, total);
+      launch_f16x2<BM, BN, WGM, 4, MODE>(a, grid, tiles_n, total, st);
     else if (vec && a.split == 1)
       gemm_kernel<BM, BN, WGM, 4, true, MODE, 1><<<grid, 256, 0, st>>>(a, tiles_n, total);
     else if (vec && split)

@@ -28,6 +28,20 @@ def gemm_force_config(cfg: int = -1, stream_k: int = -1) -> None:
     call("sfx_gemm_force_config", cfg, stream_k)
 
 
+def gemm_force_epilogue(cls: int = -1) -> None:
+    """Test hook: 0 = every GEMM launch runs the general epilogue, -1 = automatic (specialised classes where they
+    apply; bitwise equal results)."""
+    call("sfx_gemm_force_epilogue", cls)
+
+
+EPI_GENERAL, EPI_LIN, EPI_LIN_GELU, EPI_PAIR_STORE = 0, 1, 2, 3  # csrc/gemm_common.h Epi
+
+
+def gemm_last_epilogue() -> int:
+    """Epilogue class of the latest GEMM launch of the process (EPI_*; -1 before the first)."""
+    return int(_lib.fn("sfx_gemm_last_epilogue")())
+
+
 # Library operand-precision modes (include/sfx.h sfx_set_precision): "fp32" = fp32-accurate split operands (the
 # default), "amp" = reference precision, the class of the reference's fp16 autocast training (train.py:240,
 # configs/train/default.gin:11 enable_amp): leading fp16 term product only in the GEMM family.
