@@ -513,6 +513,42 @@ int sfx_rasterize_bwd_quad(int tiles_x, int tiles_y, int block_width, int img_h,
                            const float* opacity, const float* background, const float* final_Ts, const int* final_idx,
                            const float* v_out, const float* v_out_alpha, float* v_xy, float* v_xy_abs, float* v_conic,
                            float* v_rgb, float* v_opacity, void* stream);
+/* (ABI v16, additive) backward of the batched-views render, for training on the same pass the eval path renders
+ * with (gs_render.rasterize_gaussians_to_multiimgs_batched).
+ * sfx_rasterize_bwd_views_quad = sfx_rasterize_bwd_quad over the multi-view list: grid (tiles_x, tiles_y, views);
+ * tile_bins [views * tiles][2]; gids_sorted indexes Gaussian-views (view * n + i) and, like final_idx, refers to the
+ * one sorted list of all views; final_Ts / final_idx [views][H][W] as written by sfx_rasterize_fwd_views_quad;
+ * v_out [views][H][W][3]; v_out_alpha [views][H][W] or NULL; xys / conics / colors / opacity per Gaussian-view
+ * ([views * n][.], the forward's operands).  v_xy [views * n][2], v_conic [.][3], v_rgb [.][3], v_opacity [.] and
+ * v_xy_abs ([.][2], or NULL) are accumulated (+=) with float atomics: zero them first.  block_width must be 16. */
+int sfx_rasterize_bwd_views_quad(int views, int tiles_x, int tiles_y, int block_width, int img_h, int img_w,
+                                 const int32_t* gids_sorted, const int* tile_bins, const float* xys,
+                                 const float* conics, const float* colors, const float* opacity,
+                                 const float* background, const float* final_Ts, const int* final_idx,
+                                 const float* v_out, const float* v_out_alpha, float* v_xy, float* v_xy_abs,
+                                 float* v_conic, float* v_rgb, float* v_opacity, void* stream);
+/* sfx_render_prep_project_views_bwd: backward of sfx_render_prep_project_views with respect to the RAW attributes.
+ * Inputs: the forward's attributes (pointer + row stride in floats each; features_rest may be NULL when
+ * num_bases == 1), camera_to_worlds [views][4][4], fx / fy, the forward's radii [views][n] and conics
+ * [views][n][3], and the per-Gaussian-view gradients v_xys [views][n][2], v_conics [.][3], v_rgbs [.][3],
+ * v_opacities [views][n] (the outputs of sfx_rasterize_bwd_views_quad).  Outputs, each through its own pointer +
+ * row stride (so they may be columns of one [n][C] record): v_means [n][3], v_log_scales [n][3], v_quats_raw
+ * [n][4], v_opac_logit [n][1], v_features_dc [n][3], v_features_rest [n][3 (num_bases - 1)] (NULL allowed when
+ * num_bases == 1).  Every output element is stored exactly once (plain stores: nothing to zero, no atomics,
+ * bitwise reproducible); columns of a shared record that belong to no attribute are not touched.  A view where
+ * radii <= 0 contributes nothing; view directions carry no gradient; the SH clamp passes gradient where
+ * rgb + 0.5 >= 0; v_depth and v_compensation are taken as zero. */
+int sfx_render_prep_project_views_bwd(int n, int views, int num_bases, const float* means, long long ld_means,
+                                      const float* log_scales, long long ld_scales, const float* quats_raw,
+                                      long long ld_quats, const float* opac_logit, long long ld_opac,
+                                      const float* features_dc, long long ld_dc, const float* features_rest,
+                                      long long ld_rest, const float* camera_to_worlds, float fx, float fy,
+                                      const int* radii, const float* conics, const float* v_xys,
+                                      const float* v_conics, const float* v_rgbs, const float* v_opacities,
+                                      float* v_means, long long ld_v_means, float* v_log_scales,
+                                      long long ld_v_scales, float* v_quats_raw, long long ld_v_quats,
+                                      float* v_opac_logit, long long ld_v_opac, float* v_features_dc,
+                                      long long ld_v_dc, float* v_features_rest, long long ld_v_rest, void* stream);
 /* (ABI v16, additive) gsplat rasterize_forward / rasterize_backward for any channel count 1 <= channels <= 32
  * (depth maps, normals, feature vectors): colors [N,channels], background [channels], out_img and v_out
  * [H,W,channels], v_colors [N,channels]; everything else as sfx_rasterize_fwd / sfx_rasterize_bwd, over gsplat's

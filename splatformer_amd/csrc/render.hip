@@ -152,6 +152,25 @@ __device__ __forceinline__ M3 quat_to_rotmat(float qw, float qx, float qy, float
   return R;
 }
 
+// cov3d = R S S^T R^T (scale_rot_to_cov3d), the full symmetric 3x3; it does not depend on the view
+__device__ __forceinline__ void scale_rot_to_cov3d(float sc0, float sc1, float sc2, float glob_scale, float qw,
+                                                   float qx, float qy, float qz, float (&V)[3][3]) {
+#pragma clang fp contract(off)
+  const M3 R = quat_to_rotmat(qw, qx, qy, qz);
+  const float s0 = glob_scale * sc0, s1 = glob_scale * sc1, s2 = glob_scale * sc2;
+  float M[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    M[r][0] = R.m[r][0] * s0;
+    M[r][1] = R.m[r][1] * s1;
+    M[r][2] = R.m[r][2] * s2;
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) V[r][c] = (M[r][0] * M[c][0] + M[r][1] * M[c][1]) + M[r][2] * M[c][2];
+}
+
 __device__ __forceinline__ void get_tile_bbox(float cx, float cy, float radius, int tiles_x, int tiles_y, int bw,
                                               int& x0, int& y0, int& x1, int& y1) {
   // gsplat get_tile_bbox/get_bbox: (int) truncation, clamp to [0, tiles]
@@ -184,21 +203,8 @@ __device__ __forceinline__ void project_point(int i, float px, float py, float p
   const float tz = vm[8] * px + vm[9] * py + vm[10] * pz + vm[11];
   do {
     if (tz <= clip_thresh) break;
-    // cov3d = R S S^T R^T
-    const M3 R = quat_to_rotmat(qw, qx, qy, qz);
-    const float s0 = glob_scale * sc0, s1 = glob_scale * sc1, s2 = glob_scale * sc2;
-    float M[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      M[r][0] = R.m[r][0] * s0;
-      M[r][1] = R.m[r][1] * s1;
-      M[r][2] = R.m[r][2] * s2;
-    }
     float V[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) V[r][c] = (M[r][0] * M[c][0] + M[r][1] * M[c][1]) + M[r][2] * M[c][2];
+    scale_rot_to_cov3d(sc0, sc1, sc2, glob_scale, qw, qx, qy, qz, V);
     cv[0] = V[0][0]; cv[1] = V[0][1]; cv[2] = V[0][2];
     cv[3] = V[1][1]; cv[4] = V[1][2]; cv[5] = V[2][2];
     // EWA: t clamped to 1.3 tan_fov frustum
@@ -299,6 +305,97 @@ struct PrepStrides {
   long long means, scales, quats, opac, dc, rest;
 };
 
+// The per-view pieces of the prep, shared by the forward kernel and its backward (the canonical glue arithmetic of
+// oracle/render_ref.py glue_args(canonical=True): no contraction, left-to-right sums, correctly rounded sqrt).
+// camera v: R = c2w[:3,:3] diag(1,-1,-1); viewmat = [R^T | -R^T t]
+__device__ __forceinline__ void view_camera(const float* __restrict__ c2w, float (&t)[3], float (&vm)[12]) {
+#pragma clang fp contract(off)
+  float R[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    R[r][0] = c2w[4 * r + 0];
+    R[r][1] = -c2w[4 * r + 1];
+    R[r][2] = -c2w[4 * r + 2];
+    t[r] = c2w[4 * r + 3];
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vm[4 * r + c] = R[c][r];
+    vm[4 * r + 3] = -((R[0][r] * t[0] + R[1][r] * t[1]) + R[2][r] * t[2]);
+  }
+}
+
+// unit view direction of a Gaussian at p from the camera at t (normalised by the glue, then by gsplat's SH kernel)
+__device__ __forceinline__ void view_dir(float px, float py, float pz, const float (&t)[3], float& x, float& y,
+                                         float& z) {
+#pragma clang fp contract(off)
+  float vx = px - t[0], vy = py - t[1], vz = pz - t[2];
+  const float vn = sqrtf((vx * vx + vy * vy) + vz * vz);
+  if (vn == 0.f) {  // reference draws a random direction here (gs_utils.py:72-76); we use +z
+    vx = 0.f; vy = 0.f; vz = 1.f;
+  } else {
+    vx /= vn; vy /= vn; vz /= vn;
+  }
+  const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
+  x = vx / nrm; y = vy / nrm; z = vz / nrm;
+}
+
+// channel ch of the SH colour before the +0.5 / clamp: d0 = the dc coefficient, c[3 * k + ch] the coefficient of
+// basis k >= 1 (compile-time indices once ch is unrolled: the array stays in registers)
+template <int DEG>
+__device__ __forceinline__ float sh_color(const float (&c)[3 * (DEG + 1) * (DEG + 1)], float d0, int ch, float x,
+                                          float y, float z) {
+#pragma clang fp contract(off)
+  const float xx = x * x, xy = x * y, xz = x * z, yy = y * y, yz = y * z, zz = z * z;
+  float acc = SH_C0 * d0;
+  if constexpr (DEG >= 1) acc += SH_C1 * (-y * c[3 + ch] + z * c[6 + ch] - x * c[9 + ch]);
+  if constexpr (DEG >= 2) {
+    acc += (SH_C2[0] * xy * c[12 + ch] + SH_C2[1] * yz * c[15 + ch] + SH_C2[2] * (2.f * zz - xx - yy) * c[18 + ch] +
+            SH_C2[3] * xz * c[21 + ch] + SH_C2[4] * (xx - yy) * c[24 + ch]);
+  }
+  if constexpr (DEG >= 3) {
+    acc += (SH_C3[0] * y * (3.f * xx - yy) * c[27 + ch] + SH_C3[1] * xy * z * c[30 + ch] +
+            SH_C3[2] * y * (4.f * zz - xx - yy) * c[33 + ch] +
+            SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * c[36 + ch] +
+            SH_C3[4] * x * (4.f * zz - xx - yy) * c[39 + ch] + SH_C3[5] * z * (xx - yy) * c[42 + ch] +
+            SH_C3[6] * x * (xx - 3.f * yy) * c[45 + ch]);
+  }
+  if constexpr (DEG >= 4) {
+    acc += (SH_C4[0] * xy * (xx - yy) * c[48 + ch] + SH_C4[1] * yz * (3.f * xx - yy) * c[51 + ch] +
+            SH_C4[2] * xy * (7.f * zz - 1.f) * c[54 + ch] + SH_C4[3] * yz * (7.f * zz - 3.f) * c[57 + ch] +
+            SH_C4[4] * (zz * (35.f * zz - 30.f) + 3.f) * c[60 + ch] + SH_C4[5] * xz * (7.f * zz - 3.f) * c[63 + ch] +
+            SH_C4[6] * (xx - yy) * (7.f * zz - 1.f) * c[66 + ch] + SH_C4[7] * xz * (xx - 3.f * yy) * c[69 + ch] +
+            SH_C4[8] * (xx * (xx - 3.f * yy) - yy * (3.f * xx - yy)) * c[72 + ch]);
+  }
+  return acc;
+}
+
+// The view-independent glue of one Gaussian: activated scales, normalised quaternion (NaN -> identity, `subst`),
+// sigmoid opacity -- fp64 exps rounded once.
+struct PrepPoint {
+  float px, py, pz, sc0, sc1, sc2, q0, q1, q2, q3, qn, op;
+  bool subst;
+};
+
+__device__ __forceinline__ PrepPoint prep_point(const float* __restrict__ mp, const float* __restrict__ sp,
+                                                const float* __restrict__ qp, float opac_logit) {
+#pragma clang fp contract(off)
+  PrepPoint g;
+  g.px = mp[0]; g.py = mp[1]; g.pz = mp[2];
+  g.sc0 = (float)exp((double)sp[0]); g.sc1 = (float)exp((double)sp[1]); g.sc2 = (float)exp((double)sp[2]);
+  float q0 = qp[0], q1 = qp[1], q2 = qp[2], q3 = qp[3];
+  g.qn = sqrtf(((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3);
+  q0 /= g.qn; q1 /= g.qn; q2 /= g.qn; q3 /= g.qn;
+  g.subst = isnan(q0) || isnan(q1) || isnan(q2) || isnan(q3);
+  if (g.subst) {
+    q0 = 0.f; q1 = 0.f; q2 = 0.f; q3 = 1.f;
+  }
+  g.q0 = q0; g.q1 = q1; g.q2 = q2; g.q3 = q3;
+  g.op = (float)(1.0 / (1.0 + exp(-(double)opac_logit)));
+  return g;
+}
+
 // One thread per Gaussian, all views in a loop: the Gaussian's parameters (up to 75 SH floats) are read once into
 // registers and its view-independent terms (exp scales, normalised quaternion, sigmoid opacity -- fp64 exps) computed
 // once, instead of once per (Gaussian, view) thread re-reading them (config E: 9 views x 500k x 59 floats).  The
@@ -316,44 +413,18 @@ __global__ void __launch_bounds__(256) render_prep_project_kernel(
 #pragma clang fp contract(off)
   constexpr int NB = (DEG + 1) * (DEG + 1);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  // camera v: R = c2w[:3,:3] diag(1,-1,-1); viewmat = [R^T | -R^T t]
-  auto camera = [&](int v, float (&t)[3], float (&vm)[12]) {
-    const float* c2w = c2ws + 16 * v;
-    float R[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      R[r][0] = c2w[4 * r + 0];
-      R[r][1] = -c2w[4 * r + 1];
-      R[r][2] = -c2w[4 * r + 2];
-      t[r] = c2w[4 * r + 3];
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) vm[4 * r + c] = R[c][r];
-      vm[4 * r + 3] = -((R[0][r] * t[0] + R[1][r] * t[1]) + R[2][r] * t[2]);
-    }
-  };
   if (i == 0 && viewmat_out) {
     float t[3], vm[12];
-    camera(0, t, vm);
+    view_camera(c2ws, t, vm);
 #pragma unroll
     for (int k = 0; k < 12; ++k) viewmat_out[k] = vm[k];
   }
   if (i >= n) return;
-  const float* mp = means + i * ld.means;
-  const float* sp = log_scales + i * ld.scales;
-  const float* qp = quats_raw + i * ld.quats;
   const float* dcp = dc + i * ld.dc;
-  const float px = mp[0], py = mp[1], pz = mp[2];
-  const float sc0 = (float)exp((double)sp[0]), sc1 = (float)exp((double)sp[1]), sc2 = (float)exp((double)sp[2]);
-  float q0 = qp[0], q1 = qp[1], q2 = qp[2], q3 = qp[3];
-  const float qn = sqrtf(((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3);
-  q0 /= qn; q1 /= qn; q2 /= qn; q3 /= qn;
-  if (isnan(q0) || isnan(q1) || isnan(q2) || isnan(q3)) {
-    q0 = 0.f; q1 = 0.f; q2 = 0.f; q3 = 1.f;
-  }
-  const float op = (float)(1.0 / (1.0 + exp(-(double)opac_logit[i * ld.opac])));
+  const PrepPoint g = prep_point(means + i * ld.means, log_scales + i * ld.scales, quats_raw + i * ld.quats,
+                                 opac_logit[i * ld.opac]);
+  const float px = g.px, py = g.py, pz = g.pz, sc0 = g.sc0, sc1 = g.sc1, sc2 = g.sc2;
+  const float q0 = g.q0, q1 = g.q1, q2 = g.q2, q3 = g.q3, op = g.op;
   float d0[3];
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) d0[ch] = dcp[ch];
@@ -367,49 +438,17 @@ __global__ void __launch_bounds__(256) render_prep_project_kernel(
   }
   for (int v = 0; v < nviews; ++v) {
     float t[3], vm[12];
-    camera(v, t, vm);
+    view_camera(c2ws + 16 * v, t, vm);
     const long long o = (long long)v * n;
     opac[o + i] = op;
     if constexpr (DEG == 0) {
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) rgbs[3 * (o + i) + ch] = rgb0[ch];
     } else {
-      float vx = px - t[0], vy = py - t[1], vz = pz - t[2];
-      const float vn = sqrtf((vx * vx + vy * vy) + vz * vz);
-      if (vn == 0.f) {  // reference draws a random direction here (gs_utils.py:72-76); we use +z
-        vx = 0.f; vy = 0.f; vz = 1.f;
-      } else {
-        vx /= vn; vy /= vn; vz /= vn;
-      }
-      const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
-      const float x = vx / nrm, y = vy / nrm, z = vz / nrm;
-      const float xx = x * x, xy = x * y, xz = x * z, yy = y * y, yz = y * z, zz = z * z;
+      float x, y, z;
+      view_dir(px, py, pz, t, x, y, z);
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        float acc = SH_C0 * d0[ch];
-        acc += SH_C1 * (-y * c[3 + ch] + z * c[6 + ch] - x * c[9 + ch]);
-        if constexpr (DEG >= 2) {
-          acc += (SH_C2[0] * xy * c[12 + ch] + SH_C2[1] * yz * c[15 + ch] + SH_C2[2] * (2.f * zz - xx - yy) * c[18 + ch] +
-                  SH_C2[3] * xz * c[21 + ch] + SH_C2[4] * (xx - yy) * c[24 + ch]);
-          if constexpr (DEG >= 3) {
-            acc += (SH_C3[0] * y * (3.f * xx - yy) * c[27 + ch] + SH_C3[1] * xy * z * c[30 + ch] +
-                    SH_C3[2] * y * (4.f * zz - xx - yy) * c[33 + ch] +
-                    SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * c[36 + ch] +
-                    SH_C3[4] * x * (4.f * zz - xx - yy) * c[39 + ch] + SH_C3[5] * z * (xx - yy) * c[42 + ch] +
-                    SH_C3[6] * x * (xx - 3.f * yy) * c[45 + ch]);
-            if constexpr (DEG >= 4) {
-              acc += (SH_C4[0] * xy * (xx - yy) * c[48 + ch] + SH_C4[1] * yz * (3.f * xx - yy) * c[51 + ch] +
-                      SH_C4[2] * xy * (7.f * zz - 1.f) * c[54 + ch] + SH_C4[3] * yz * (7.f * zz - 3.f) * c[57 + ch] +
-                      SH_C4[4] * (zz * (35.f * zz - 30.f) + 3.f) * c[60 + ch] +
-                      SH_C4[5] * xz * (7.f * zz - 3.f) * c[63 + ch] +
-                      SH_C4[6] * (xx - yy) * (7.f * zz - 1.f) * c[66 + ch] +
-                      SH_C4[7] * xz * (xx - 3.f * yy) * c[69 + ch] +
-                      SH_C4[8] * (xx * (xx - 3.f * yy) - yy * (3.f * xx - yy)) * c[72 + ch]);
-            }
-          }
-        }
-        rgbs[3 * (o + i) + ch] = fmaxf(acc + 0.5f, 0.f);
-      }
+      for (int ch = 0; ch < 3; ++ch) rgbs[3 * (o + i) + ch] = fmaxf(sh_color<DEG>(c, d0[ch], ch, x, y, z) + 0.5f, 0.f);
     }
     project_point(i, px, py, pz, sc0, sc1, sc2, q0, q1, q2, q3, 1.f, vm, fx, fy, cx, cy, img_h, img_w, bw, 0.01f,
                   xys + 2 * o, depths + o, radii + o, conics + 3 * o, nullptr, num_tiles_hit + o, nullptr);
@@ -451,6 +490,149 @@ int launch_prep(int n, int nviews, int num_bases, const float* means, const floa
 // backward of project (gsplat project_gaussians_backward_kernel semantics: the
 // EWA Jacobian uses the *unclamped* camera-space mean, and the quaternion
 // gradient is taken w.r.t. the normalised quaternion).
+// One Gaussian of project_gaussians_backward_kernel (the caller has checked radii > 0): viewmat vm, activated scales
+// sc, the (normalised) quaternion, the forward's cov3d cv[6] and conic cn, upstream gradients -> v_mean (vm_out),
+// v_scale, v_quat and the intermediate v_cov2d / v_cov3d.  WITH_COMP = false: v_compensation is zero (the batched
+// training path, whose forward keeps no compensation).
+template <bool WITH_COMP>
+__device__ __forceinline__ void project_bwd_point(float px, float py, float pz, float sc0, float sc1, float sc2,
+                                                  float glob_scale, float qw, float qx, float qy, float qz,
+                                                  const float (&vm)[12], float fx, float fy, const float (&cv)[6],
+                                                  float cn0, float cn1, float cn2, float cmp, float v_xy0,
+                                                  float v_xy1, float v_depth, float v_cn0, float v_cn1, float v_cn2,
+                                                  float v_comp, float (&vm_out)[3], float (&vs_out)[3],
+                                                  float (&vq_out)[4], float (&vc2)[3], float (&vc3)[6]) {
+  const float tx = vm[0] * px + vm[1] * py + vm[2] * pz + vm[3];
+  const float ty = vm[4] * px + vm[5] * py + vm[6] * pz + vm[7];
+  const float tz = vm[8] * px + vm[9] * py + vm[10] * pz + vm[11];
+  // v_mean from v_xy (project_pix_vjp) + rot-only transpose
+  {
+    const float rw = 1.f / (tz + 1e-6f);
+    const float vpx = fx * v_xy0, vpy = fy * v_xy1;
+    const float v0 = vpx * rw, v1 = vpy * rw, v2 = -(vpx * tx + vpy * ty) * rw * rw;
+    vm_out[0] = vm[0] * v0 + vm[4] * v1 + vm[8] * v2;
+    vm_out[1] = vm[1] * v0 + vm[5] * v1 + vm[9] * v2;
+    vm_out[2] = vm[2] * v0 + vm[6] * v1 + vm[10] * v2;
+    const float vz = v_depth;
+    vm_out[0] += vm[8] * vz;
+    vm_out[1] += vm[9] * vz;
+    vm_out[2] += vm[10] * vz;
+  }
+  // v_cov2d from v_conic (cov2d_to_conic_vjp) and v_comp
+  const float X0 = cn0, X1 = cn1, X2 = cn2;
+  {
+    const float G0 = v_cn0, G1 = 0.5f * v_cn1, G2 = v_cn2;
+    // v_Sigma = -X G X  (symmetric 2x2)
+    const float XG00 = X0 * G0 + X1 * G1, XG01 = X0 * G1 + X1 * G2;
+    const float XG10 = X1 * G0 + X2 * G1, XG11 = X1 * G1 + X2 * G2;
+    const float s00 = -(XG00 * X0 + XG01 * X1);
+    const float s01 = -(XG00 * X1 + XG01 * X2);
+    const float s10 = -(XG10 * X0 + XG11 * X1);
+    const float s11 = -(XG10 * X1 + XG11 * X2);
+    vc2[0] = s00;
+    vc2[1] = s10 + s01;
+    vc2[2] = s11;
+    if constexpr (WITH_COMP) {
+      const float inv_det = X0 * X2 - X1 * X1;
+      const float one_m = 1.f - cmp * cmp;
+      const float vsq = v_comp * 0.5f / (cmp + 1e-6f);
+      vc2[0] += vsq * (one_m * X0 - 0.3f * inv_det);
+      vc2[1] += 2.f * vsq * (one_m * X1);
+      vc2[2] += vsq * (one_m * X2 - 0.3f * inv_det);
+    }
+  }
+  // v_cov3d and v_mean contribution (project_cov3d_ewa_vjp)
+  float V[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
+  const float rz = 1.f / tz, rz2 = rz * rz, rz3 = rz2 * rz;
+  // T = J W (2 rows used; J row 2 is zero)
+  const float j00 = fx * rz, j02 = -fx * tx * rz2, j11 = fy * rz, j12 = -fy * ty * rz2;
+  float T[3][3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    T[0][c] = j00 * vm[0 + c] + j02 * vm[8 + c];
+    T[1][c] = j11 * vm[4 + c] + j12 * vm[8 + c];
+    T[2][c] = 0.f;
+  }
+  float G[3][3] = {{vc2[0], 0.5f * vc2[1], 0.f}, {0.5f * vc2[1], vc2[2], 0.f}, {0.f, 0.f, 0.f}};
+  // v_V = T^T G T
+  float GT[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) GT[r][c] = G[r][0] * T[0][c] + G[r][1] * T[1][c] + G[r][2] * T[2][c];
+  float vV[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vV[r][c] = T[0][r] * GT[0][c] + T[1][r] * GT[1][c] + T[2][r] * GT[2][c];
+  vc3[0] = vV[0][0];
+  vc3[1] = vV[0][1] + vV[1][0];
+  vc3[2] = vV[0][2] + vV[2][0];
+  vc3[3] = vV[1][1];
+  vc3[4] = vV[1][2] + vV[2][1];
+  vc3[5] = vV[2][2];
+  // v_T = G T V^T + G^T T V  (V symmetric, G symmetric -> 2 G T V)
+  float vT[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float gtv = GT[r][0] * V[c][0] + GT[r][1] * V[c][1] + GT[r][2] * V[c][2];  // (G T V^T)[r][c]
+      const float gtv2 = GT[r][0] * V[0][c] + GT[r][1] * V[1][c] + GT[r][2] * V[2][c];  // (G^T T V)[r][c]
+      vT[r][c] = gtv + gtv2;
+    }
+  // v_J = v_T W^T
+  float vJ[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vJ[r][c] = vT[r][0] * vm[4 * c + 0] + vT[r][1] * vm[4 * c + 1] + vT[r][2] * vm[4 * c + 2];
+  const float vt0 = -fx * rz2 * vJ[0][2];
+  const float vt1 = -fy * rz2 * vJ[1][2];
+  const float vt2 = -fx * rz2 * vJ[0][0] + 2.f * fx * tx * rz3 * vJ[0][2] - fy * rz2 * vJ[1][1] +
+                    2.f * fy * ty * rz3 * vJ[1][2];
+  vm_out[0] += vt0 * vm[0] + vt1 * vm[4] + vt2 * vm[8];
+  vm_out[1] += vt0 * vm[1] + vt1 * vm[5] + vt2 * vm[9];
+  vm_out[2] += vt0 * vm[2] + vt1 * vm[6] + vt2 * vm[10];
+
+  // scale / quat (scale_rot_to_cov3d_vjp)
+  const M3 R = quat_to_rotmat(qw, qx, qy, qz);
+  const float s[3] = {glob_scale * sc0, glob_scale * sc1, glob_scale * sc2};
+  float vVs[3][3] = {{vc3[0], 0.5f * vc3[1], 0.5f * vc3[2]},
+                     {0.5f * vc3[1], vc3[3], 0.5f * vc3[4]},
+                     {0.5f * vc3[2], 0.5f * vc3[4], vc3[5]}};
+  float Mm[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Mm[r][c] = R.m[r][c] * s[c];
+  float vM[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vM[r][c] = 2.f * (vVs[r][0] * Mm[0][c] + vVs[r][1] * Mm[1][c] + vVs[r][2] * Mm[2][c]);
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    vs_out[c] = (R.m[0][c] * vM[0][c] + R.m[1][c] * vM[1][c] + R.m[2][c] * vM[2][c]) * glob_scale;
+  float vR[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vR[r][c] = vM[r][c] * s[c];
+  // quat_to_rotmat_vjp with glm column-major v_R[col][row] == vR[row][col]
+  const float sn = rsqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+  const float w = qw * sn, x = qx * sn, y = qy * sn, z = qz * sn;
+#define VR(col, row) vR[row][col]
+  vq_out[0] = 2.f * (x * (VR(1, 2) - VR(2, 1)) + y * (VR(2, 0) - VR(0, 2)) + z * (VR(0, 1) - VR(1, 0)));
+  vq_out[1] = 2.f * (-2.f * x * (VR(1, 1) + VR(2, 2)) + y * (VR(0, 1) + VR(1, 0)) + z * (VR(0, 2) + VR(2, 0)) +
+                     w * (VR(1, 2) - VR(2, 1)));
+  vq_out[2] = 2.f * (x * (VR(0, 1) + VR(1, 0)) - 2.f * y * (VR(0, 0) + VR(2, 2)) + z * (VR(1, 2) + VR(2, 1)) +
+                     w * (VR(2, 0) - VR(0, 2)));
+  vq_out[3] = 2.f * (x * (VR(0, 2) + VR(2, 0)) + y * (VR(1, 2) + VR(2, 1)) - 2.f * z * (VR(0, 0) + VR(1, 1)) +
+                     w * (VR(0, 1) - VR(1, 0)));
+#undef VR
+}
+
 __global__ void project_bwd_kernel(int n, const float* __restrict__ means, const float* __restrict__ scales,
                                    float glob_scale, const float* __restrict__ quats,
                                    const float* __restrict__ viewmat, float fx, float fy,
@@ -466,140 +648,16 @@ __global__ void project_bwd_kernel(int n, const float* __restrict__ means, const
   float vm_out[3] = {0.f, 0.f, 0.f}, vs_out[3] = {0.f, 0.f, 0.f}, vq_out[4] = {0.f, 0.f, 0.f, 0.f};
   float vc2[3] = {0.f, 0.f, 0.f}, vc3[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (radii[i] > 0) {
-    float vm[12];
+    float vm[12], cv[6];
 #pragma unroll
     for (int k = 0; k < 12; ++k) vm[k] = viewmat[k];
-    const float px = means[3 * i], py = means[3 * i + 1], pz = means[3 * i + 2];
-    const float tx = vm[0] * px + vm[1] * py + vm[2] * pz + vm[3];
-    const float ty = vm[4] * px + vm[5] * py + vm[6] * pz + vm[7];
-    const float tz = vm[8] * px + vm[9] * py + vm[10] * pz + vm[11];
-    // v_mean from v_xy (project_pix_vjp) + rot-only transpose
-    {
-      const float rw = 1.f / (tz + 1e-6f);
-      const float vpx = fx * v_xy[2 * i], vpy = fy * v_xy[2 * i + 1];
-      const float v0 = vpx * rw, v1 = vpy * rw, v2 = -(vpx * tx + vpy * ty) * rw * rw;
-      vm_out[0] = vm[0] * v0 + vm[4] * v1 + vm[8] * v2;
-      vm_out[1] = vm[1] * v0 + vm[5] * v1 + vm[9] * v2;
-      vm_out[2] = vm[2] * v0 + vm[6] * v1 + vm[10] * v2;
-      const float vz = v_depth[i];
-      vm_out[0] += vm[8] * vz;
-      vm_out[1] += vm[9] * vz;
-      vm_out[2] += vm[10] * vz;
-    }
-    // v_cov2d from v_conic (cov2d_to_conic_vjp) and v_comp
-    const float X0 = conics[3 * i], X1 = conics[3 * i + 1], X2 = conics[3 * i + 2];
-    {
-      const float G0 = v_conic[3 * i], G1 = 0.5f * v_conic[3 * i + 1], G2 = v_conic[3 * i + 2];
-      // v_Sigma = -X G X  (symmetric 2x2)
-      const float XG00 = X0 * G0 + X1 * G1, XG01 = X0 * G1 + X1 * G2;
-      const float XG10 = X1 * G0 + X2 * G1, XG11 = X1 * G1 + X2 * G2;
-      const float s00 = -(XG00 * X0 + XG01 * X1);
-      const float s01 = -(XG00 * X1 + XG01 * X2);
-      const float s10 = -(XG10 * X0 + XG11 * X1);
-      const float s11 = -(XG10 * X1 + XG11 * X2);
-      vc2[0] = s00;
-      vc2[1] = s10 + s01;
-      vc2[2] = s11;
-      const float cmp = compensation[i];
-      const float inv_det = X0 * X2 - X1 * X1;
-      const float one_m = 1.f - cmp * cmp;
-      const float vsq = v_comp[i] * 0.5f / (cmp + 1e-6f);
-      vc2[0] += vsq * (one_m * X0 - 0.3f * inv_det);
-      vc2[1] += 2.f * vsq * (one_m * X1);
-      vc2[2] += vsq * (one_m * X2 - 0.3f * inv_det);
-    }
-    // v_cov3d and v_mean contribution (project_cov3d_ewa_vjp)
-    const float* cv = cov3d + 6 * i;
-    float V[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
-    const float rz = 1.f / tz, rz2 = rz * rz, rz3 = rz2 * rz;
-    // T = J W (2 rows used; J row 2 is zero)
-    const float j00 = fx * rz, j02 = -fx * tx * rz2, j11 = fy * rz, j12 = -fy * ty * rz2;
-    float T[3][3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      T[0][c] = j00 * vm[0 + c] + j02 * vm[8 + c];
-      T[1][c] = j11 * vm[4 + c] + j12 * vm[8 + c];
-      T[2][c] = 0.f;
-    }
-    float G[3][3] = {{vc2[0], 0.5f * vc2[1], 0.f}, {0.5f * vc2[1], vc2[2], 0.f}, {0.f, 0.f, 0.f}};
-    // v_V = T^T G T
-    float GT[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) GT[r][c] = G[r][0] * T[0][c] + G[r][1] * T[1][c] + G[r][2] * T[2][c];
-    float vV[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) vV[r][c] = T[0][r] * GT[0][c] + T[1][r] * GT[1][c] + T[2][r] * GT[2][c];
-    vc3[0] = vV[0][0];
-    vc3[1] = vV[0][1] + vV[1][0];
-    vc3[2] = vV[0][2] + vV[2][0];
-    vc3[3] = vV[1][1];
-    vc3[4] = vV[1][2] + vV[2][1];
-    vc3[5] = vV[2][2];
-    // v_T = G T V^T + G^T T V  (V symmetric, G symmetric -> 2 G T V)
-    float vT[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float gtv = GT[r][0] * V[c][0] + GT[r][1] * V[c][1] + GT[r][2] * V[c][2];  // (G T V^T)[r][c]
-        const float gtv2 = GT[r][0] * V[0][c] + GT[r][1] * V[1][c] + GT[r][2] * V[2][c];  // (G^T T V)[r][c]
-        vT[r][c] = gtv + gtv2;
-      }
-    // v_J = v_T W^T
-    float vJ[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) vJ[r][c] = vT[r][0] * vm[4 * c + 0] + vT[r][1] * vm[4 * c + 1] + vT[r][2] * vm[4 * c + 2];
-    const float vt0 = -fx * rz2 * vJ[0][2];
-    const float vt1 = -fy * rz2 * vJ[1][2];
-    const float vt2 = -fx * rz2 * vJ[0][0] + 2.f * fx * tx * rz3 * vJ[0][2] - fy * rz2 * vJ[1][1] +
-                      2.f * fy * ty * rz3 * vJ[1][2];
-    vm_out[0] += vt0 * vm[0] + vt1 * vm[4] + vt2 * vm[8];
-    vm_out[1] += vt0 * vm[1] + vt1 * vm[5] + vt2 * vm[9];
-    vm_out[2] += vt0 * vm[2] + vt1 * vm[6] + vt2 * vm[10];
-
-    // scale / quat (scale_rot_to_cov3d_vjp)
-    const float qw = quats[4 * i], qx = quats[4 * i + 1], qy = quats[4 * i + 2], qz = quats[4 * i + 3];
-    const M3 R = quat_to_rotmat(qw, qx, qy, qz);
-    const float s[3] = {glob_scale * scales[3 * i], glob_scale * scales[3 * i + 1], glob_scale * scales[3 * i + 2]};
-    float vVs[3][3] = {{vc3[0], 0.5f * vc3[1], 0.5f * vc3[2]},
-                       {0.5f * vc3[1], vc3[3], 0.5f * vc3[4]},
-                       {0.5f * vc3[2], 0.5f * vc3[4], vc3[5]}};
-    float Mm[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) Mm[r][c] = R.m[r][c] * s[c];
-    float vM[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) vM[r][c] = 2.f * (vVs[r][0] * Mm[0][c] + vVs[r][1] * Mm[1][c] + vVs[r][2] * Mm[2][c]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      vs_out[c] = (R.m[0][c] * vM[0][c] + R.m[1][c] * vM[1][c] + R.m[2][c] * vM[2][c]) * glob_scale;
-    float vR[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) vR[r][c] = vM[r][c] * s[c];
-    // quat_to_rotmat_vjp with glm column-major v_R[col][row] == vR[row][col]
-    const float sn = rsqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-    const float w = qw * sn, x = qx * sn, y = qy * sn, z = qz * sn;
-#define VR(col, row) vR[row][col]
-    vq_out[0] = 2.f * (x * (VR(1, 2) - VR(2, 1)) + y * (VR(2, 0) - VR(0, 2)) + z * (VR(0, 1) - VR(1, 0)));
-    vq_out[1] = 2.f * (-2.f * x * (VR(1, 1) + VR(2, 2)) + y * (VR(0, 1) + VR(1, 0)) + z * (VR(0, 2) + VR(2, 0)) +
-                       w * (VR(1, 2) - VR(2, 1)));
-    vq_out[2] = 2.f * (x * (VR(0, 1) + VR(1, 0)) - 2.f * y * (VR(0, 0) + VR(2, 2)) + z * (VR(1, 2) + VR(2, 1)) +
-                       w * (VR(2, 0) - VR(0, 2)));
-    vq_out[3] = 2.f * (x * (VR(0, 2) + VR(2, 0)) + y * (VR(1, 2) + VR(2, 1)) - 2.f * z * (VR(0, 0) + VR(1, 1)) +
-                       w * (VR(0, 1) - VR(1, 0)));
-#undef VR
+    for (int k = 0; k < 6; ++k) cv[k] = cov3d[6 * i + k];
+    project_bwd_point<true>(means[3 * i], means[3 * i + 1], means[3 * i + 2], scales[3 * i], scales[3 * i + 1],
+                            scales[3 * i + 2], glob_scale, quats[4 * i], quats[4 * i + 1], quats[4 * i + 2],
+                            quats[4 * i + 3], vm, fx, fy, cv, conics[3 * i], conics[3 * i + 1], conics[3 * i + 2],
+                            compensation[i], v_xy[2 * i], v_xy[2 * i + 1], v_depth[i], v_conic[3 * i],
+                            v_conic[3 * i + 1], v_conic[3 * i + 2], v_comp[i], vm_out, vs_out, vq_out, vc2, vc3);
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -614,6 +672,110 @@ __global__ void project_bwd_kernel(int n, const float* __restrict__ means, const
   if (v_cov3d_out)
 #pragma unroll
     for (int k = 0; k < 6; ++k) v_cov3d_out[6 * i + k] = vc3[k];
+}
+
+// Backward of render_prep_project_kernel (the batched training render): one thread per Gaussian, all views in a
+// loop, like the forward.  The view-independent terms (exp scales, normalised quaternion, sigmoid, cov3d) are
+// recomputed once; each view adds project_bwd_point and the SH backward of its per-Gaussian-view gradients
+// (a view where radii <= 0 adds nothing) into register sums; the sums go through the glue derivatives (exp,
+// quaternion normalisation, sigmoid, the degree-0 sigmoid colour) and every output element is stored exactly once:
+// no atomics, no zero-fill, bitwise reproducible.  View directions carry no gradient (the reference takes them
+// from means.detach()); clamp(rgb + 0.5, min=0) passes gradient where rgb + 0.5 >= 0, as torch.clamp.  The
+// coefficient and gradient arrays are indexed with compile-time constants only (registers, no scratch).
+struct PrepGradPtrs {
+  float *means, *scales, *quats, *opac, *dc, *rest;
+};
+
+template <int DEG>
+__global__ void __launch_bounds__(256) render_prep_project_bwd_kernel(
+    int n, int nviews, const float* __restrict__ means, const float* __restrict__ log_scales,
+    const float* __restrict__ quats_raw, const float* __restrict__ opac_logit, const float* __restrict__ dc,
+    const float* __restrict__ rest, PrepStrides ld, const float* __restrict__ c2ws, float fx, float fy,
+    const int* __restrict__ radii, const float* __restrict__ conics, const float* __restrict__ v_xys,
+    const float* __restrict__ v_conics, const float* __restrict__ v_rgbs, const float* __restrict__ v_opacities,
+    PrepGradPtrs out, PrepStrides ldo) {
+  constexpr int NB = (DEG + 1) * (DEG + 1);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const PrepPoint g = prep_point(means + i * ld.means, log_scales + i * ld.scales, quats_raw + i * ld.quats,
+                                 opac_logit[i * ld.opac]);
+  float d0[3];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) d0[ch] = dc[i * ld.dc + ch];
+  float c[3 * NB];  // as the forward: c[3 * k + ch], k >= 1 (needed for the clamp mask only)
+#pragma unroll
+  for (int k = 3; k < 3 * NB; ++k) c[k] = rest[i * ld.rest + (k - 3)];
+  float V[3][3];
+  scale_rot_to_cov3d(g.sc0, g.sc1, g.sc2, 1.f, g.q0, g.q1, g.q2, g.q3, V);
+  const float cv[6] = {V[0][0], V[0][1], V[0][2], V[1][1], V[1][2], V[2][2]};
+
+  float s_mean[3] = {0.f, 0.f, 0.f}, s_scale[3] = {0.f, 0.f, 0.f}, s_quat[4] = {0.f, 0.f, 0.f, 0.f};
+  float s_op = 0.f;
+  float s_c[3 * NB];  // d(loss) / d(SH coefficient k, channel ch) at 3 * k + ch; degree 0: d / d(rgb)
+#pragma unroll
+  for (int k = 0; k < 3 * NB; ++k) s_c[k] = 0.f;
+
+  for (int v = 0; v < nviews; ++v) {
+    const long long r = (long long)v * n + i;
+    if (radii[r] <= 0) continue;
+    float t[3], vm[12];
+    view_camera(c2ws + 16 * v, t, vm);
+    float vm_out[3], vs_out[3], vq_out[4], vc2[3], vc3[6];
+    project_bwd_point<false>(g.px, g.py, g.pz, g.sc0, g.sc1, g.sc2, 1.f, g.q0, g.q1, g.q2, g.q3, vm, fx, fy, cv,
+                             conics[3 * r], conics[3 * r + 1], conics[3 * r + 2], 0.f, v_xys[2 * r],
+                             v_xys[2 * r + 1], 0.f, v_conics[3 * r], v_conics[3 * r + 1], v_conics[3 * r + 2], 0.f,
+                             vm_out, vs_out, vq_out, vc2, vc3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      s_mean[k] += vm_out[k];
+      s_scale[k] += vs_out[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s_quat[k] += vq_out[k];
+    s_op += v_opacities[r];
+    if constexpr (DEG == 0) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) s_c[ch] += v_rgbs[3 * r + ch];
+    } else {
+      float x, y, z;
+      view_dir(g.px, g.py, g.pz, t, x, y, z);
+      float b[25];
+      sh_basis(DEG, x, y, z, b);
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const float gc = (sh_color<DEG>(c, d0[ch], ch, x, y, z) + 0.5f >= 0.f) ? v_rgbs[3 * r + ch] : 0.f;
+#pragma unroll
+        for (int k = 0; k < NB; ++k) s_c[3 * k + ch] += b[k] * gc;
+      }
+    }
+  }
+
+  // glue derivatives
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out.means[i * ldo.means + k] = s_mean[k];
+  out.scales[i * ldo.scales + 0] = s_scale[0] * g.sc0;  // d exp(s) = exp(s)
+  out.scales[i * ldo.scales + 1] = s_scale[1] * g.sc1;
+  out.scales[i * ldo.scales + 2] = s_scale[2] * g.sc2;
+  {  // q_hat = q / |q|: (v - q_hat (q_hat . v)) / |q|; nothing where the forward substituted the identity
+    const float dot = s_quat[0] * g.q0 + s_quat[1] * g.q1 + s_quat[2] * g.q2 + s_quat[3] * g.q3;
+    const float rn = 1.f / g.qn;
+    const float qh[4] = {g.q0, g.q1, g.q2, g.q3};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out.quats[i * ldo.quats + k] = g.subst ? 0.f : (s_quat[k] - qh[k] * dot) * rn;
+  }
+  out.opac[i * ldo.opac] = s_op * g.op * (1.f - g.op);
+  if constexpr (DEG == 0) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {  // rgb = sigmoid(dc), fp64 rounded once as the forward
+      const float rgb = (float)(1.0 / (1.0 + exp(-(double)d0[ch])));
+      out.dc[i * ldo.dc + ch] = s_c[ch] * rgb * (1.f - rgb);
+    }
+  } else {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) out.dc[i * ldo.dc + ch] = s_c[ch];
+#pragma unroll
+    for (int k = 3; k < 3 * NB; ++k) out.rest[i * ldo.rest + (k - 3)] = s_c[k];
+  }
 }
 
 // ---- intersections ----------------------------------------------------------
@@ -1325,7 +1487,15 @@ rasterize_bwd_quad_kernel(int tiles_x, int tiles_y, int img_h, int img_w, const 
   __shared__ unsigned char mask_batch[BS];
   __shared__ unsigned char wlist[4][BS];
 
-  const int tile_id = blockIdx.y * tiles_x + blockIdx.x;
+  // batched views (sfx_rasterize_bwd_views_quad): blockIdx.z = view, as rasterize_fwd_quad_kernel -- tiles numbered
+  // per view, per-view image planes; gids_sorted / final_idx index the one multi-view list, the per-Gaussian
+  // operands and gradients are per Gaussian-view
+  const int tile_id = blockIdx.z * tiles_x * tiles_y + blockIdx.y * tiles_x + blockIdx.x;
+  if (blockIdx.z > 0) {
+    const long long po = (long long)blockIdx.z * img_h * img_w;
+    final_Ts += po; final_idx += po; v_out += 3 * po;
+    if (v_out_alpha) v_out_alpha += po;
+  }
   const int tr = threadIdx.x;
   const int lane = tr & 63, w = tr >> 6;
   const int qx = (w & 1) * 8, qy = (w >> 1) * 8;
@@ -1801,6 +1971,73 @@ int sfx_rasterize_bwd_quad(int tiles_x, int tiles_y, int block_width, int img_h,
       tiles_x, tiles_y, img_h, img_w, gids_sorted, tile_bins, xys, conics, colors, opacity, background, final_Ts,
       final_idx, v_out, v_out_alpha, v_xy, v_xy_abs, v_conic, v_rgb, v_opacity);
   return sfx::check_launch("sfx_rasterize_bwd_quad");
+}
+
+// ---- batched views, backward (the training render of rasterize_gaussians_to_multiimgs_batched) --------------
+int sfx_rasterize_bwd_views_quad(int views, int tiles_x, int tiles_y, int block_width, int img_h, int img_w,
+                                 const int32_t* gids_sorted, const int* tile_bins, const float* xys,
+                                 const float* conics, const float* colors, const float* opacity,
+                                 const float* background, const float* final_Ts, const int* final_idx,
+                                 const float* v_out, const float* v_out_alpha, float* v_xy, float* v_xy_abs,
+                                 float* v_conic, float* v_rgb, float* v_opacity, void* stream) {
+  SFX_REQUIRE(views >= 1 && views <= 65535, "sfx_rasterize_bwd_views_quad: views must be in [1,65535]");
+  SFX_REQUIRE(block_width == 16, "sfx_rasterize_bwd_views_quad: block_width must be 16");
+  SFX_REQUIRE(img_h > 0 && img_w > 0 && tiles_x == (img_w + 15) / 16 && tiles_y == (img_h + 15) / 16,
+              "sfx_rasterize_bwd_views_quad: tile bounds do not match the image size");
+  SFX_REQUIRE(gids_sorted && tile_bins && xys && conics && colors && opacity && background && final_Ts && final_idx &&
+                  v_out && v_xy && v_conic && v_rgb && v_opacity,
+              "sfx_rasterize_bwd_views_quad: null buffer");
+  dim3 grid(tiles_x, tiles_y, views);
+  rasterize_bwd_quad_kernel<<<grid, 256, 0, sfx::as_stream(stream)>>>(
+      tiles_x, tiles_y, img_h, img_w, gids_sorted, tile_bins, xys, conics, colors, opacity, background, final_Ts,
+      final_idx, v_out, v_out_alpha, v_xy, v_xy_abs, v_conic, v_rgb, v_opacity);
+  return sfx::check_launch("sfx_rasterize_bwd_views_quad");
+}
+
+int sfx_render_prep_project_views_bwd(int n, int views, int num_bases, const float* means, long long ld_means,
+                                      const float* log_scales, long long ld_scales, const float* quats_raw,
+                                      long long ld_quats, const float* opac_logit, long long ld_opac,
+                                      const float* features_dc, long long ld_dc, const float* features_rest,
+                                      long long ld_rest, const float* camera_to_worlds, float fx, float fy,
+                                      const int* radii, const float* conics, const float* v_xys,
+                                      const float* v_conics, const float* v_rgbs, const float* v_opacities,
+                                      float* v_means, long long ld_v_means, float* v_log_scales,
+                                      long long ld_v_scales, float* v_quats_raw, long long ld_v_quats,
+                                      float* v_opac_logit, long long ld_v_opac, float* v_features_dc,
+                                      long long ld_v_dc, float* v_features_rest, long long ld_v_rest, void* stream) {
+  SFX_REQUIRE(n >= 0, "sfx_render_prep_project_views_bwd: n < 0");
+  SFX_REQUIRE(views >= 1 && views <= 65535, "sfx_render_prep_project_views_bwd: views must be in [1,65535]");
+  SFX_REQUIRE((long long)n * views < (1ll << 31), "sfx_render_prep_project_views_bwd: views * n must fit int32");
+  SFX_REQUIRE(num_bases == 1 || num_bases == 4 || num_bases == 9 || num_bases == 16 || num_bases == 25,
+              "sfx_render_prep_project_views_bwd: num_bases must be a square in {1,4,9,16,25}");
+  SFX_REQUIRE(camera_to_worlds, "sfx_render_prep_project_views_bwd: null cameras");
+  if (n == 0) return SFX_OK;
+  SFX_REQUIRE(means && log_scales && quats_raw && opac_logit && features_dc && (num_bases == 1 || features_rest),
+              "sfx_render_prep_project_views_bwd: null input buffer");
+  SFX_REQUIRE(radii && conics && v_xys && v_conics && v_rgbs && v_opacities,
+              "sfx_render_prep_project_views_bwd: null per-view buffer");
+  SFX_REQUIRE(v_means && v_log_scales && v_quats_raw && v_opac_logit && v_features_dc &&
+                  (num_bases == 1 || v_features_rest),
+              "sfx_render_prep_project_views_bwd: null gradient buffer");
+  const PrepStrides ld{ld_means, ld_scales, ld_quats, ld_opac, ld_dc, ld_rest};
+  const PrepStrides ldo{ld_v_means, ld_v_scales, ld_v_quats, ld_v_opac, ld_v_dc, ld_v_rest};
+  const PrepGradPtrs out{v_means, v_log_scales, v_quats_raw, v_opac_logit, v_features_dc, v_features_rest};
+  const unsigned blocks = sfx::ceil_div(n, 256);
+  hipStream_t st = sfx::as_stream(stream);
+#define SFX_PREP_BWD(DG)                                                                                          \
+  render_prep_project_bwd_kernel<DG><<<blocks, 256, 0, st>>>(n, views, means, log_scales, quats_raw, opac_logit,   \
+                                                             features_dc, features_rest, ld, camera_to_worlds, fx, \
+                                                             fy, radii, conics, v_xys, v_conics, v_rgbs,           \
+                                                             v_opacities, out, ldo)
+  switch (num_bases) {
+    case 1: SFX_PREP_BWD(0); break;
+    case 4: SFX_PREP_BWD(1); break;
+    case 9: SFX_PREP_BWD(2); break;
+    case 16: SFX_PREP_BWD(3); break;
+    default: SFX_PREP_BWD(4); break;
+  }
+#undef SFX_PREP_BWD
+  return sfx::check_launch("sfx_render_prep_project_views_bwd");
 }
 
 }  // extern "C"

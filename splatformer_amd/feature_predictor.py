@@ -206,6 +206,14 @@ class FeaturePredictor(nn.Module):
             self.__dict__["_fused_heads_cache"] = cache
         return cache[1], cache[2], cache[3], cache[4]
 
+    def columns(self) -> Dict[str, tuple]:
+        """name -> (first column, width) of each output feature in the packed record (unpack's layout)."""
+        cols, c = OrderedDict(), 0
+        for f in self.output_features:
+            cols[f] = (c, self.ch[f])
+            c += self.ch[f]
+        return cols
+
     def unpack(self, packed: Tensor) -> Dict[str, Tensor]:
         out = OrderedDict()
         c = 0

@@ -10,6 +10,10 @@ reference signatures (gs_utils.py:20, :29).  Two device paths, both HIP:
 * training (params require grad): the reference's torch glue around the
   autograd Functions of `gsplat_compat` so gradients flow to the refined
   Gaussians (reference train.py:273-289).
+
+`rasterize_gaussians_to_multiimgs_batched` / `rasterize_packed_to_multiimgs_batched` differentiate the eval path's
+own batched pass over all views instead (backward: `sfx_rasterize_bwd_views_quad`, then
+`sfx_render_prep_project_views_bwd`).
 """
 from __future__ import annotations
 
@@ -200,6 +204,15 @@ def render_views_meta(gs_params: Dict[str, Tensor], cameras: Dict):
 
 
 def _render_fused_views(gs, c2ws, cameras, meta=None):
+    out, alpha, _ = _fused_views_pass(gs, c2ws, cameras, True, meta)
+    return list(out.unbind(0)), list(alpha.unsqueeze(-1).unbind(0))
+
+
+def _fused_views_pass(gs, c2ws, cameras, clamp_max1=True, meta=None):
+    """The batched pass over all views -> (out [V, H, W, 3], alpha [V, H, W], state).  clamp_max1: the image clamp
+    of gs_utils.py:111 fused into the rasterizer (eval); False leaves the image unclamped for a caller whose
+    autograd owns that clamp (the batched training render).  state: what a backward over the same list needs
+    (per-view projection outputs, sorted ids, bins, final T / index); `lists` is False when no list was built."""
     means = gs["means"]
     _lib.require_gpu(means)
     dev = means.device
@@ -291,15 +304,20 @@ def _render_fused_views(gs, c2ws, cameras, meta=None):
         call("sfx_tile_bins", total, ptr(isect_s), V * T, ptr(bins), stream())
         final_Ts, final_idx = f(V, H, W), f(V, H, W, dt=torch.int32)
         call("sfx_rasterize_fwd_views_quad" if cull else "sfx_rasterize_fwd_views_packed", V, tiles_x, tiles_y, bw,
-             H, W, ptr(gids_s), ptr(bins), ptr(rec), ptr(bg), 1, ptr(final_Ts), ptr(final_idx), ptr(out),
-             ptr(alpha), stream())
+             H, W, ptr(gids_s), ptr(bins), ptr(rec), ptr(bg), 1 if clamp_max1 else 0, ptr(final_Ts), ptr(final_idx),
+             ptr(out), ptr(alpha), stream())
     elif any(c > 0 for c in per_view):  # every gsplat intersection culled: T = 1 at every pixel of those views
-        out[:] = torch.clamp(bg, max=1.0)
+        out[:] = torch.clamp(bg, max=1.0) if clamp_max1 else bg
         alpha.zero_()
     for v in range(V):
         if per_view[v] < 1:
-            out[v] = torch.clamp(bg, max=1.0).expand(H, W, 3)
+            out[v] = (torch.clamp(bg, max=1.0) if clamp_max1 else bg).expand(H, W, 3)
             alpha[v] = 1.0
+    state = dict(lists=total > 0, n=n, V=V, H=H, W=W, nb=nb, fx=fx, fy=fy, tiles_x=tiles_x, tiles_y=tiles_y, bg=bg,
+                 cams=cams, rgbs=rgbs, opacities=opac, xys=xys, radii=radii, conics=conics, keep=keep,
+                 attrs=(pm, lm, ps, ls, pq, lq, po, lo, pd, ldc, pr, lr))
+    if total > 0:
+        state.update(gids_sorted=gids_s, tile_bins=bins, final_Ts=final_Ts, final_idx=final_idx)
     if meta is not None:
         meta.update(rgbs=rgbs, opacities=opac, xys=xys, depths=depths, radii=radii, conics=conics,
                     num_tiles_hit=tiles.view(V, n), num_tiles_kept=kept.view(V, n), per_view=per_view, tiles_x=tiles_x,
@@ -307,7 +325,7 @@ def _render_fused_views(gs, c2ws, cameras, meta=None):
         if total > 0:
             meta.update(isect_sorted=isect_s, gids_sorted=gids_s, tile_bins=bins.view(V, T, 2), final_Ts=final_Ts,
                         final_idx=final_idx)
-    return list(out.unbind(0)), list(alpha.unsqueeze(-1).unbind(0))
+    return out, alpha, state
 
 
 def _autograd_prep(gs_params):
@@ -377,6 +395,129 @@ def _render_autograd(gs_params, camera_to_world, cx, cy, fx, fy, W, H, backgroun
     return rgb, alpha
 
 
+# ---- batched differentiable render (training on the eval path's pass) ------------------------------------------
+ATTRIBUTES = ("means", "scales", "quats", "opacities", "features_dc", "features_rest")
+
+
+class _RenderViewsBatched(torch.autograd.Function):
+    """All views of a scene in ONE pass, differentiable with respect to the packed record [N, C] whose columns
+    `cols[name] = (first column, width)` hold the raw attributes (FeaturePredictor.unpack's layout).  Forward:
+    _fused_views_pass, the eval path's own sequence, with the image left unclamped (the wrapper clamps, so autograd
+    owns that mask).  Backward: one zero-fill, sfx_rasterize_bwd_views_quad over the same multi-view list, then
+    sfx_render_prep_project_views_bwd writing the [N, C] gradient in one launch.  Attributes outside the record
+    (`extra`) are constants."""
+
+    @staticmethod
+    def forward(ctx, packed, cols, extra, c2ws, cameras):
+        rec = packed.detach()
+        if rec.dtype != torch.float32 or not rec.is_contiguous():
+            rec = rec.float().contiguous()
+        gs = {}
+        for name in ATTRIBUTES:
+            if name in cols:
+                c0, w = cols[name]
+                v = rec[:, c0:c0 + w]
+                gs[name] = v.unflatten(1, (-1, 3)) if name == "features_rest" else v
+            elif name in extra:
+                gs[name] = extra[name].detach().float()
+            elif name != "features_rest":
+                raise ValueError(f"No {name} found in the packed record or the extra attributes")
+        out, alpha, st = _fused_views_pass(gs, c2ws, cameras, clamp_max1=False)
+        ctx.st, ctx.cols, ctx.shape = st, dict(cols), tuple(rec.shape)
+        ctx.save_for_backward(packed)  # the backward re-reads the record in place: autograd checks it is unmodified
+        ctx.set_materialize_grads(False)
+        return out, alpha
+
+    @staticmethod
+    def backward(ctx, v_out, v_alpha):
+        st, cols, _ = ctx.st, ctx.cols, ctx.saved_tensors
+        N, C = ctx.shape
+        dev = st["bg"].device
+        covered = sum(w for _, w in cols.values()) == C
+        if not st["lists"] or (v_out is None and v_alpha is None) or N == 0:
+            return torch.zeros(N, C, device=dev), None, None, None, None
+        n, V, H, W, nb = st["n"], st["V"], st["H"], st["W"], st["nb"]
+        v_out = torch.zeros(V, H, W, 3, device=dev) if v_out is None else v_out.float().contiguous()
+        v_alpha = None if v_alpha is None else v_alpha.float().contiguous()
+        g = torch.zeros(V * n * 9, device=dev)  # [v_xy | v_conic | v_rgb | v_opacity], accumulated with atomics
+        v_xy, v_conic, v_rgb, v_op = g[:2 * V * n], g[2 * V * n:5 * V * n], g[5 * V * n:8 * V * n], g[8 * V * n:]
+        call("sfx_rasterize_bwd_views_quad", V, st["tiles_x"], st["tiles_y"], BLOCK_WIDTH, H, W, ptr(st["gids_sorted"]),
+             ptr(st["tile_bins"]), ptr(st["xys"]), ptr(st["conics"]), ptr(st["rgbs"]), ptr(st["opacities"]),
+             ptr(st["bg"]), ptr(st["final_Ts"]), ptr(st["final_idx"]), ptr(v_out), ptr(v_alpha), ptr(v_xy), None,
+             ptr(v_conic), ptr(v_rgb), ptr(v_op), stream())
+        grad = torch.empty(N, C, device=dev) if covered else torch.zeros(N, C, device=dev)
+        spill = []  # gradients of the constant attributes: written, never read
+
+        def dst(name, width):
+            if name in cols:
+                return grad.data_ptr() + 4 * cols[name][0], C
+            spill.append(torch.empty(N, width, device=dev))
+            return spill[-1].data_ptr(), width
+
+        outs = []
+        for name, width in (("means", 3), ("scales", 3), ("quats", 4), ("opacities", 1), ("features_dc", 3),
+                            ("features_rest", 3 * (nb - 1))):
+            outs += list(dst(name, width)) if width else [None, 0]
+        call("sfx_render_prep_project_views_bwd", n, V, nb, *st["attrs"], ptr(st["cams"]), st["fx"], st["fy"],
+             ptr(st["radii"]), ptr(st["conics"]), ptr(v_xy), ptr(v_conic), ptr(v_rgb), ptr(v_op), *outs, stream())
+        return grad, None, None, None, None
+
+
+def rasterize_packed_to_multiimgs_batched(packed: Tensor, columns: Dict[str, Tuple[int, int]], cameras: Dict,
+                                          extra: Dict[str, Tensor] = None) -> Tuple[List[Tensor], List[Tensor]]:
+    """rasterize_gaussians_to_multiimgs_batched for Gaussians held as one packed record [N, C]: columns[name] =
+    (first column, width) of the raw attribute `name` (FeaturePredictor.columns()); `extra`: attributes the record
+    does not hold (constants).  The gradient with respect to `packed` is written by one launch."""
+    c2ws = cameras["camera_to_worlds"]
+    c2ws = c2ws if isinstance(c2ws, Tensor) else torch.stack(list(c2ws))
+    cams = {k: v for k, v in cameras.items() if k != "camera_to_worlds"}
+    out, alpha = _RenderViewsBatched.apply(packed, columns, extra or {}, c2ws, cams)
+    rgb = torch.clamp(out, max=1.0)
+    return list(rgb.unbind(0)), list(alpha.unsqueeze(-1).unbind(0))
+
+
+def _record_of(gs: Dict[str, Tensor]):
+    """(record, columns) when every attribute of `gs` is a column range of one contiguous float32 [N, C] tensor
+    (the views FeaturePredictor.unpack makes of a packed record), else None."""
+    base = cols = None
+    for name, t in gs.items():
+        b = t._base
+        if b is None or (base is not None and b is not base) or b.dim() != 2 or not b.is_contiguous() or \
+                b.dtype != torch.float32 or t.dtype != torch.float32:
+            return None
+        base, cols = b, cols or {}
+        w = math.prod(t.shape[1:])
+        flat_ok = (t.dim() == 2 and t.stride() == (b.shape[1], 1)) or \
+                  (t.dim() == 3 and t.stride() == (b.shape[1], 3, 1) and t.shape[2] == 3)
+        if not flat_ok or w == 0 or t.storage_offset() + w > b.shape[1]:
+            return None
+        cols[name] = (t.storage_offset(), w)
+    return base, cols
+
+
+def rasterize_gaussians_to_multiimgs_batched(gs_params: Dict[str, Tensor], cameras: Dict
+                                             ) -> Tuple[List[Tensor], List[Tensor]]:
+    """rasterize_gaussians_to_multiimgs (same signature and returns), differentiable, with every view rendered in
+    the eval path's single batched pass and the backward in two launches (sfx_rasterize_bwd_views_quad,
+    sfx_render_prep_project_views_bwd).  Attributes that are already columns of one record (FeaturePredictor.unpack
+    of a leaf) are used in place; otherwise the dict is packed with one torch.cat."""
+    if "opacities" not in gs_params:
+        raise ValueError("No opacities found in gs_params (the batched render takes opacity logits)")
+    gp = {k: gs_params[k] for k in ATTRIBUTES if k in gs_params}
+    gp = {k: v.float() if v.dtype == torch.half else v for k, v in gp.items()}
+    rec = _record_of(gp)
+    if rec is None:
+        n = gp["means"].shape[0]
+        cols, c0 = {}, 0
+        for k, v in gp.items():
+            w = math.prod(v.shape[1:])
+            cols[k] = (c0, w)
+            c0 += w
+        rec = torch.cat([v.reshape(n, -1).float() for v in gp.values()], 1), cols
+    return rasterize_packed_to_multiimgs_batched(rec[0], rec[1], cameras)
+
+
 __all__ = ["rasterize_gaussians_to_multiimgs", "rasterize_gaussians_to_singleimg", "rasterize_gaussians_to_rgbd",
            "rasterize_gaussians_to_multirgbd", "render_views_meta", "BLOCK_WIDTH", "SH2RGB", "RGB2SH",
+           "rasterize_gaussians_to_multiimgs_batched", "rasterize_packed_to_multiimgs_batched",
            "bin_and_sort_gaussians", "compute_cumulative_intersects"]

@@ -1,7 +1,8 @@
 """Training step of SplatFormer on MI355X (reference train.py:236-303, configs C/D).
 
 Per scene: FeaturePredictor forward in train mode (ptv3_train), the refined Gaussians rendered to the
-training views through the gsplat-compatible autograd path (gs_render / gsplat_compat HIP kernels), the
+training views through the gsplat-compatible autograd path (gs_render / gsplat_compat HIP kernels; or, with
+render="batched", through the eval path's single batched pass and its two-launch backward), the
 image L1 loss `sum_v |pred_v - gt_v|.mean() / num_images / len(batch)` (train.py:272-283, image_l1 weight 1;
 the LPIPS term needs VGG weights that are not available offline and is left out), backward through the
 renderer to the packed refined record, then the hand-written refiner backward.  Every `accumulate_step`
@@ -23,7 +24,9 @@ from . import ptv3_train as pt
 from . import train_ops as tops
 from .dist import allreduce_mean_
 from .feature_predictor import ALL_FEATURES, FeaturePredictor
-from .gs_render import rasterize_gaussians_to_multiimgs
+from .gs_render import rasterize_gaussians_to_multiimgs, rasterize_packed_to_multiimgs_batched
+
+RENDER_MODES = ("per_view", "batched")
 
 
 # ---- FeaturePredictor train forward / backward --------------------------------------------------------------
@@ -101,15 +104,22 @@ class Trainer:
 
     def __init__(self, model: FeaturePredictor, lr: float = 3e-5, eps: float = 1e-15, betas=(0.9, 0.999),
                  grad_clip_norm: float = 2.0, accumulate_step: int = 1, group=None, generator=None,
-                 precision: Optional[str] = None):
+                 precision: Optional[str] = None, render: Optional[str] = None):
         """precision: "fp32" (default; fp32-accurate refiner forward + backward) or "amp", the reference's
         `training.enable_amp` (train.py:214-299, configs/train/default.gin:11): refiner forward and backward in
         the autocast precision class (ptv3_ops.precision); the renderer, loss and optimiser stay fp32 as in the
         reference (its rasterisation runs outside the autocast region).  No loss scale: the GEMMs scale every
         operand row by its own power of two, so fp16 range limits never flush or overflow a gradient; GradScaler's
         skip of a step with non-finite gradients is kept (optimizer_step).
-        Default from SFX_TRAIN_PREC."""
+        Default from SFX_TRAIN_PREC.
+        render: "per_view" (default; the reference's loop over the views through the gsplat-compatible autograd ops)
+        or "batched": all views of a scene in the eval path's single pass, the packed leaf handed to
+        gs_render.rasterize_packed_to_multiimgs_batched, whose backward writes leaf.grad in one launch.  Default
+        from SFX_TRAIN_RENDER."""
         self.model = model
+        self.render = render or os.environ.get("SFX_TRAIN_RENDER", "per_view")
+        if self.render not in RENDER_MODES:
+            raise ValueError(f"render {self.render!r}: expected one of {RENDER_MODES}")
         self.precision = precision or os.environ.get("SFX_TRAIN_PREC", "fp32")
         if self.precision not in ops.PRECISIONS:
             raise ValueError(f"precision {self.precision!r}: expected one of {sorted(ops.PRECISIONS)}")
@@ -146,9 +156,17 @@ class Trainer:
         for gs, cams, imgs in zip(scenes, cameras, images):
             with ops.precision(self.precision):
                 packed, tape = refine_train(self.model, gs, masks, perms=perms, group=self.group)
-            leaf, out_gs = unpack_leaf(self.model, packed, gs)
+            batched = self.render == "batched"
+            if batched:  # the packed record itself is the leaf: its gradient is written by one launch
+                leaf, out_gs = packed.detach().requires_grad_(), None
+                extra = {k: v for k, v in gs.items() if not (self.model.sh_degree == 0 and k == "features_rest")}
+            else:
+                leaf, out_gs = unpack_leaf(self.model, packed, gs)
             with torch.enable_grad():
-                preds, _ = rasterize_gaussians_to_multiimgs(out_gs, cams)
+                if batched:
+                    preds, _ = rasterize_packed_to_multiimgs_batched(leaf, self.model.columns(), cams, extra=extra)
+                else:
+                    preds, _ = rasterize_gaussians_to_multiimgs(out_gs, cams)
                 loss = image_l1(preds, imgs) / num_images / len(scenes) / self.accumulate_step
                 loss.backward()
             with ops.precision(self.precision):

@@ -1,7 +1,10 @@
 """Eval-render timing on the bench workloads (config B: 100k SH1 9 x 800x800; E: 500k SH3 9 x 1920x1080):
 the refined Gaussians of bench.py's model/scene, rendered with and without exact contribution culling
 (SFX_RENDER_CULL), per-kernel times from torch.profiler-free HIP events around the whole render plus
-intersection counts.  usage: python tools/render_bench.py [B|E] [reps]"""
+intersection counts.  usage: python tools/render_bench.py [B|E] [reps]
+Training render (4 views of the config-B scene, forward + backward): python tools/render_bench.py train (per view,
+cull off / on) | train_batched (the single batched pass); run either under rocprofv3 --kernel-trace --stats for the
+per-kernel times (every iteration, the first included, does the same work)."""
 import os
 import statistics
 import sys
@@ -77,8 +80,34 @@ def train_main(reps=5):
               f"(min {min(ts):7.3f}) |grad means| {g:.6e}", flush=True)
 
 
-if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "train":
-    train_main()
+def train_batched_main(reps=5):
+    """train_main's workload through rasterize_gaussians_to_multiimgs_batched: all 4 views in one pass, the backward
+    in two launches."""
+    n, W, H, sh = CFG["B"]
+    dev = torch.device("cuda", 0)
+    _lib.load()
+    scene = to_device(make_scene(n, sh_degree=sh, seed=0), dev)
+    cams = to_device(make_cameras(W, H, n_views=4), dev)
+    params = {k: v.clone().requires_grad_(True) for k, v in scene.items()}
+    ts = []
+    for it in range(2 * reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rgbs, _ = gs_render.rasterize_gaussians_to_multiimgs_batched(params, cams)
+        loss = sum(r.sum() for r in rgbs)
+        loss.backward()
+        torch.cuda.synchronize()
+        if it:
+            ts.append(1e3 * (time.perf_counter() - t0))
+        g = params["means"].grad.norm().item()
+        for p in params.values():
+            p.grad = None
+    print(f"train render 4 views fwd+bwd batched median {statistics.median(ts):7.3f} ms "
+          f"(min {min(ts):7.3f}) |grad means| {g:.6e}", flush=True)
+
+
+if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] in ("train", "train_batched"):
+    train_main() if sys.argv[1] == "train" else train_batched_main()
     sys.exit(0)
 
 
