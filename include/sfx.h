@@ -216,6 +216,25 @@ int sfx_linear_bwd_data(int M, int N, int K, const float* dY, long long ldy, con
 /* dW[N,K] += dY[M,N]^T X[M,K]; db[N] += sum_m dY[m,:] (db may be NULL).  Accumulates (float atomics). */
 int sfx_linear_wgrad(int M, int N, int K, const float* dY, long long ldy, const float* X, long long ldx, float* dW,
                      long long ldw, float* db, void* stream);
+/* The same with every dY row scaled first: dW += (rowscale o dY)^T X; db += sum_m rowscale[m] dY[m,:] -- the
+ * weight gradient of a Linear whose output goes through DropPath (attn.proj, mlp.fc2: rowscale = the branch's
+ * keep/(1-p) mask [M]).  The scaled rows are written to `scaled` (M*N floats, 16-byte aligned scratch) and
+ * reduced by the kernels of sfx_linear_wgrad; rowscale NULL: sfx_linear_wgrad itself (scaled unused).  Same
+ * sizes and alignment rules. */
+int sfx_linear_wgrad_rs(int M, int N, int K, const float* dY, long long ldy, const float* X, long long ldx,
+                        const float* rowscale, float* scaled, float* dW, long long ldw, float* db, void* stream);
+/* spconv SubMConv3d weight gradient (the cpe.0 conv of every Block, folded or not): for each of the 27 kernel
+ * offsets k, dW[o, k, i] += sum over the (in, out) pairs of offset k of dY[out, o] X[in, i]; dW is
+ * [Cout, 27*Cin] (spconv [Cout,3,3,3,Cin], row stride ldw); db[o] += sum_rows dY[row, o] (db may be NULL).
+ * nbr [n][27] and pair_in / pair_out / pair_off_host are the map objects sfx_subm_conv_bwd_data takes (lists
+ * without the centre offset; pair lists may be NULL when pair_off_host[27] = 0); the centre offset pairs
+ * in = nbr[i][13] with out = i.  One launch for the 27 offsets, reduction splits sized from pair_off_host.
+ * cin, cout, ldy, ldx multiples of 4, dY / X 16-byte aligned.  Accumulates (float atomics); follows
+ * sfx_set_precision as sfx_linear_wgrad does (bf16 term products: six in mode 0, three in mode 1; also under
+ * SFX_GEMM_PREC=fp32, where the six products are as accurate as fp32 arithmetic). */
+int sfx_subm_conv_wgrad(int n, int cin, int cout, const float* dy, long long ldy, const float* x, long long ldx,
+                        const int* nbr, const int* pair_in, const int* pair_out, const int* pair_off_host, float* dw,
+                        long long ldw, float* db, void* stream);
 /* dst[c, r] = src[r, c] */
 /* An empty kernel delimiting units of work in a rocprofv3 PMC / kernel trace (bench.py measure_traffic). */
 int sfx_profile_marker(int tag, void* stream);
@@ -245,6 +264,13 @@ int sfx_window_attention_varlen_bwd(int num_windows, int max_window, int heads, 
 int sfx_layernorm_bwd(int M, int C, const float* X, long long ldx, const float* gamma, const float* dY,
                       long long ldgy, const float* dR, long long ldr, float eps, float* dX, long long lddx,
                       void* stream);
+/* nn.LayerNorm affine gradients: dgamma[c] (+)= sum_m dY[m,c] xhat[m,c], dbeta[c] (+)= sum_m dY[m,c], with
+ * xhat recomputed from X (biased variance, eps); C <= 512; either output may be NULL; accumulate = 1 adds to
+ * the outputs, 0 stores.  Two-level fp64 reduction in a fixed order (deterministic); ws = workspace of
+ * sfx_layernorm_wgrad_workspace_bytes(M, C) bytes, 8-byte aligned. */
+size_t sfx_layernorm_wgrad_workspace_bytes(int M, int C);
+int sfx_layernorm_wgrad(int M, int C, const float* X, long long ldx, const float* dY, long long ldgy, float eps,
+                        void* ws, size_t ws_bytes, float* dgamma, float* dbeta, int accumulate, void* stream);
 /* Block tail backward: dX1 = dX2 + LN1'(X1) dH ; dU = LN_cpe'(U) dX1   (rows of C contiguous floats) */
 int sfx_cpe_ln_bwd(int M, int C, const float* U, const float* X1, const float* gamma_cpe, const float* gamma1,
                    const float* dX2, const float* dH, float eps, float* dX1, float* dU, void* stream);

@@ -482,17 +482,19 @@ constexpr int WG2_PLANE = WG2_T * 64;  // bytes of one term image
 
 // NQ = 2 (reference-precision mode): the two leading terms and three products t0t0, t0t1, t1t0 (16-bit
 // significands, still finer than the reference autocast's fp16 operands).
-template <int NQ>
-__global__ void __launch_bounds__(256, 2) wgrad2_kernel(int M, int N, int K, const float* __restrict__ dY,
-                                                        long long ldy, const float* __restrict__ X, long long ldx,
-                                                        float* __restrict__ dW, long long ldw, int chunk,
-                                                        float* __restrict__ db) {
+// Where the rows of the two operands come from (SRC): WG2_DENSE rows m of dY and X; WG2_PAIRS reduction index m is an
+// entry of an indice-pair list: dY row idx_y[m * istride + ioff], X row idx_x[m * istride + ioff] (a null list: row m
+// itself; a negative entry: an absent row, read as zeros).  The indices of slab s + 2 are fetched while slab
+// s + 1's rows are in flight, so the gather adds no dependent latency to the loop.
+enum { WG2_DENSE = 0, WG2_PAIRS = 1 };
+
+template <int NQ, int SRC>
+__device__ __forceinline__ void wgrad2_body(char* img, int m_begin, int m_end, int N, int K, int n0, int k0,
+                                            const float* __restrict__ dY, long long ldy, const float* __restrict__ X,
+                                            long long ldx, float* __restrict__ dW, long long ldw,
+                                            float* __restrict__ db, const int* __restrict__ idx_y, const int* __restrict__ idx_x, int istride,
+                                            int ioff) {
   typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-  __shared__ __attribute__((aligned(16))) char img[2 * 3 * WG2_PLANE];  // [dY, X][term][128 rows][64 B]
-  const int tiles_k = (K + WG2_T - 1) / WG2_T;
-  const int n0 = (blockIdx.x / tiles_k) * WG2_T, k0 = (blockIdx.x % tiles_k) * WG2_T;
-  const int m_begin = blockIdx.y * chunk;
-  const int m_end = min(M, m_begin + chunk);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, h = lane >> 5, l32 = lane & 31;
   const int wn = wid & 1, wk = wid >> 1;  // wave sub-tile: rows wn*64.., columns wk*64..
   // staging role: operand op (0 dY, 1 X), column group c4 (4 columns), point group mg (8 points)
@@ -514,14 +516,32 @@ __global__ void __launch_bounds__(256, 2) wgrad2_kernel(int M, int N, int K, con
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   float4 v[8];
+  int ix[8];    // WG2_PAIRS: the row indices of the slab after the one in v
+  const int* idx = op ? idx_x : idx_y;
+  const __amdgpu_buffer_rsrc_t rI = rsrc(SRC == WG2_PAIRS && idx ? (const void*)idx : (const void*)dY);
+  auto load_idx = [&](int m0) {
+    if constexpr (SRC == WG2_PAIRS) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int m = m0 + 8 * mg + r;
+        ix[r] = idx ? bload1i(rI, m < m_end ? ((unsigned)m * (unsigned)istride + (unsigned)ioff) * 4u : OOB) : m;
+      }
+    }
+  };
   auto load = [&](int m0) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
       const int m = m0 + 8 * mg + r;
-      v[r] = bload4(rS, (m < m_end && col_ok) ? ((unsigned)m * ld32 + (unsigned)col) * 4u : OOB);
+      if constexpr (SRC == WG2_PAIRS) {
+        v[r] = bload4(rS, (m < m_end && col_ok && ix[r] >= 0) ? ((unsigned)ix[r] * ld32 + (unsigned)col) * 4u : OOB);
+      } else {
+        v[r] = bload4(rS, (m < m_end && col_ok) ? ((unsigned)m * ld32 + (unsigned)col) * 4u : OOB);
+      }
     }
   };
+  load_idx(m_begin);
   load(m_begin);
+  load_idx(m_begin + BK);
   for (int m0 = m_begin; m0 < m_end; m0 += BK) {
     __syncthreads();  // the previous slab's fragments have been read
 #pragma unroll
@@ -541,7 +561,10 @@ __global__ void __launch_bounds__(256, 2) wgrad2_kernel(int M, int N, int K, con
             make_uint4(t0[q].x, t0[q].y, t1[q].x, t1[q].y);
     }
     __syncthreads();
-    if (m0 + BK < m_end) load(m0 + BK);  // next slab in flight during the products
+    if (m0 + BK < m_end) {  // next slab in flight during the products
+      load(m0 + BK);
+      load_idx(m0 + 2 * BK);
+    }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {  // 16-point steps
       bf16x8 af[2][3], bf[2][3];
@@ -583,6 +606,67 @@ __global__ void __launch_bounds__(256, 2) wgrad2_kernel(int M, int N, int K, con
             acc[i][j][r], rW, (n < N && k < K) ? ((unsigned)n * ldw32 + (unsigned)k) * 4u : OOB, 0, 0);
       }
     }
+}
+
+template <int NQ, int SRC>
+__global__ void __launch_bounds__(256, 2) wgrad2_kernel(int M, int N, int K, const float* __restrict__ dY,
+                                                        long long ldy, const float* __restrict__ X, long long ldx,
+                                                        float* __restrict__ dW, long long ldw, int chunk,
+                                                        float* __restrict__ db) {
+  __shared__ __attribute__((aligned(16))) char img[2 * 3 * WG2_PLANE];  // [dY, X][term][128 rows][64 B]
+  const int tiles_k = (K + WG2_T - 1) / WG2_T;
+  const int n0 = (blockIdx.x / tiles_k) * WG2_T, k0 = (blockIdx.x % tiles_k) * WG2_T;
+  const int m_begin = blockIdx.y * chunk;
+  const int m_end = min(M, m_begin + chunk);
+  wgrad2_body<NQ, SRC>(img, m_begin, m_end, N, K, n0, k0, dY, ldy, X, ldx, dW, ldw, db, nullptr, nullptr, 0, 0);
+}
+
+// ---- SubMConv3d weight gradient: dW[o, k, i] += sum over the (in, out) pairs of offset k of dY[out, o] X[in, i] ----
+// The same reduction as wgrad2_kernel, once per kernel offset, with the rows of both operands fetched through the
+// offset's indice pairs.  One launch covers the 27 offsets: grid.y enumerates (offset, reduction split) work items,
+// item_off[k] .. item_off[k + 1] being offset k's, so an offset with few pairs (the corner offsets of a sparse
+// stage) gets as many workgroups as its pairs fill and no empty ones.  The centre offset k = 13 reads no list:
+// out = row i, in = nbr[i][13] (the lowest point index of a duplicated voxel), and its workgroups also sum db.
+struct SubmWgradPlan {
+  int pair_off[28];  // prefix of the pair counts per offset (centre: none)
+  int item_off[28];  // prefix of the work items per offset (centre: its n rows)
+  int chunk;         // reduction entries per work item (multiple of BK)
+};
+
+template <int NQ>
+__global__ void __launch_bounds__(256, 2) subm_wgrad_kernel(int n, int cin, int cout, const float* __restrict__ dY,
+                                                            long long ldy, const float* __restrict__ X, long long ldx,
+                                                            const int* __restrict__ nbr,
+                                                            const int* __restrict__ pair_in,
+                                                            const int* __restrict__ pair_out, SubmWgradPlan plan,
+                                                            float* __restrict__ dW, long long ldw,
+                                                            float* __restrict__ db) {
+  __shared__ __attribute__((aligned(16))) char img[2 * 3 * WG2_PLANE];
+  const int tiles_k = (cin + WG2_T - 1) / WG2_T;
+  const int n0 = (blockIdx.x / tiles_k) * WG2_T, k0 = (blockIdx.x % tiles_k) * WG2_T;
+  const int item = blockIdx.y;
+  int k = 0;
+  while (k < 26 && item >= plan.item_off[k + 1]) ++k;
+  const bool centre = k == 13;
+  const int base = centre ? 0 : plan.pair_off[k];
+  const int count = centre ? n : plan.pair_off[k + 1] - base;
+  const int m_begin = base + (item - plan.item_off[k]) * plan.chunk;
+  const int m_end = min(base + count, m_begin + plan.chunk);
+  wgrad2_body<NQ, WG2_PAIRS>(img, m_begin, m_end, cout, cin, n0, k0, dY, ldy, X, ldx, dW + (long long)k * cin, ldw,
+                             centre ? db : nullptr, centre ? nullptr : pair_out, centre ? nbr : pair_in,
+                             centre ? 27 : 1, centre ? 13 : 0);
+}
+
+// out[m][:] = rowscale[m] * dY[m][:]  (contiguous rows of n4 float4: the row-scaled weight gradient's operand)
+__global__ void __launch_bounds__(256) rowscale_rows_kernel(int M, int n4, const float* __restrict__ dY, long long ldy,
+                                                            const float* __restrict__ rowscale,
+                                                            float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)M * n4) return;
+  const int m = (int)(i / n4), c = (int)(i % n4) * 4;
+  const float s = rowscale[m];
+  const float4 v = *reinterpret_cast<const float4*>(dY + (long long)m * ldy + c);
+  *reinterpret_cast<float4*>(out + i * 4) = make_float4(v.x * s, v.y * s, v.z * s, v.w * s);
 }
 
 // dst[c][r] = src[r][c]
@@ -875,15 +959,15 @@ int sfx_set_precision(int mode) {
 
 int sfx_get_precision(void) { return g_prec; }
 
-int sfx_linear_wgrad(int M, int N, int K, const float* dY, long long ldy, const float* X, long long ldx, float* dW,
-                     long long ldw, float* db, void* stream) {
-  SFX_REQUIRE(M >= 0 && N > 0 && K > 0, "sfx_linear_wgrad: bad sizes M=%d N=%d K=%d", M, N, K);
+static int linear_wgrad(const char* what, int M, int N, int K, const float* dY, long long ldy, const float* X,
+                        long long ldx, float* dW, long long ldw, float* db, void* stream) {
+  SFX_REQUIRE(M >= 0 && N > 0 && K > 0, "%s: bad sizes M=%d N=%d K=%d", what, M, N, K);
   if (M == 0) return SFX_OK;
-  SFX_REQUIRE(dY && X && dW, "sfx_linear_wgrad: null buffer");
+  SFX_REQUIRE(dY && X && dW, "%s: null buffer", what);
   SFX_REQUIRE(N % 4 == 0 && K % 4 == 0 && ldy % 4 == 0 && ldx % 4 == 0 && aligned16(dY) && aligned16(X),
-              "sfx_linear_wgrad: N, K, leading dims must be multiples of 4 and operands 16-byte aligned");
-  SFX_REQUIRE(ldy >= N && ldx >= K && ldw >= K, "sfx_linear_wgrad: leading dim");
-  SFX_REQUIRE(fits(M, ldy) && fits(M, ldx) && fits(N, ldw), "sfx_linear_wgrad: operand exceeds 2 GiB range");
+              "%s: N, K, leading dims must be multiples of 4 and operands 16-byte aligned", what);
+  SFX_REQUIRE(ldy >= N && ldx >= K && ldw >= K, "%s: leading dim", what);
+  SFX_REQUIRE(fits(M, ldy) && fits(M, ldx) && fits(N, ldw), "%s: operand exceeds 2 GiB range", what);
   hipStream_t st = sfx::as_stream(stream);
   const int slabs = (int)sfx::ceil_div(M, BK);
   if (split_mode(M) != 0) {  // bf16x3 terms, 128 x 128 tiles (SFX_GEMM_PREC=fp32: the exact kernel below)
@@ -894,10 +978,10 @@ int sfx_linear_wgrad(int M, int N, int K, const float* dY, long long ldy, const 
     const int chunk2 = (int)sfx::ceil_div(slabs, splits2) * BK;
     splits2 = (int)sfx::ceil_div(M, chunk2);
     if (g_prec == 1)
-      wgrad2_kernel<2><<<dim3(tiles2, splits2), 256, 0, st>>>(M, N, K, dY, ldy, X, ldx, dW, ldw, chunk2, db);
+      wgrad2_kernel<2, WG2_DENSE><<<dim3(tiles2, splits2), 256, 0, st>>>(M, N, K, dY, ldy, X, ldx, dW, ldw, chunk2, db);
     else
-      wgrad2_kernel<3><<<dim3(tiles2, splits2), 256, 0, st>>>(M, N, K, dY, ldy, X, ldx, dW, ldw, chunk2, db);
-    return sfx::check_launch("sfx_linear_wgrad");
+      wgrad2_kernel<3, WG2_DENSE><<<dim3(tiles2, splits2), 256, 0, st>>>(M, N, K, dY, ldy, X, ldx, dW, ldw, chunk2, db);
+    return sfx::check_launch(what);
   }
   const int tiles = (int)(sfx::ceil_div(N, WG_TILE) * sfx::ceil_div(K, WG_TILE));
   int splits = (int)sfx::ceil_div(4 * num_cus(), tiles);
@@ -906,7 +990,65 @@ int sfx_linear_wgrad(int M, int N, int K, const float* dY, long long ldy, const 
   const int chunk = (int)sfx::ceil_div(slabs, splits) * BK;
   splits = (int)sfx::ceil_div(M, chunk);
   wgrad_kernel<<<dim3(tiles, splits), THREADS, 0, st>>>(M, N, K, dY, ldy, X, ldx, dW, ldw, chunk, db);
-  return sfx::check_launch("sfx_linear_wgrad");
+  return sfx::check_launch(what);
+}
+
+int sfx_linear_wgrad(int M, int N, int K, const float* dY, long long ldy, const float* X, long long ldx, float* dW,
+                     long long ldw, float* db, void* stream) {
+  return linear_wgrad("sfx_linear_wgrad", M, N, K, dY, ldy, X, ldx, dW, ldw, db, stream);
+}
+
+int sfx_linear_wgrad_rs(int M, int N, int K, const float* dY, long long ldy, const float* X, long long ldx,
+                        const float* rowscale, float* scaled, float* dW, long long ldw, float* db, void* stream) {
+  if (!rowscale || M <= 0) return linear_wgrad("sfx_linear_wgrad_rs", M, N, K, dY, ldy, X, ldx, dW, ldw, db, stream);
+  SFX_REQUIRE(N > 0 && N % 4 == 0 && dY && ldy >= N && ldy % 4 == 0 && aligned16(dY) && fits(M, ldy),
+              "sfx_linear_wgrad_rs: bad dY");
+  SFX_REQUIRE(scaled && aligned16(scaled) && fits(M, N), "sfx_linear_wgrad_rs: scaled must be M*N floats, 16-byte aligned");
+  rowscale_rows_kernel<<<sfx::ceil_div((long long)M * (N / 4), 256), 256, 0, sfx::as_stream(stream)>>>(
+      M, N / 4, dY, ldy, rowscale, scaled);
+  int rc = sfx::check_launch("sfx_linear_wgrad_rs(scale)");
+  if (rc) return rc;
+  return linear_wgrad("sfx_linear_wgrad_rs", M, N, K, scaled, N, X, ldx, dW, ldw, db, stream);
+}
+
+int sfx_subm_conv_wgrad(int n, int cin, int cout, const float* dy, long long ldy, const float* x, long long ldx,
+                        const int* nbr, const int* pair_in, const int* pair_out, const int* pair_off_host, float* dw,
+                        long long ldw, float* db, void* stream) {
+  SFX_REQUIRE(n >= 0 && cin > 0 && cout > 0, "sfx_subm_conv_wgrad: bad sizes");
+  if (n == 0) return SFX_OK;
+  SFX_REQUIRE(dy && x && nbr && dw && pair_off_host, "sfx_subm_conv_wgrad: null buffer");
+  SFX_REQUIRE(cin % 4 == 0 && cout % 4 == 0 && ldy % 4 == 0 && ldx % 4 == 0 && aligned16(dy) && aligned16(x),
+              "sfx_subm_conv_wgrad: channels and leading dims must be multiples of 4 and operands 16-byte aligned");
+  SFX_REQUIRE(ldy >= cout && ldx >= cin && ldw >= 27ll * cin, "sfx_subm_conv_wgrad: leading dimension too small");
+  SFX_REQUIRE(fits(n, ldy) && fits(n, ldx) && fits(cout, ldw) && fits(n, 27),
+              "sfx_subm_conv_wgrad: operand exceeds the 2 GiB buffer-descriptor range");
+  const int pairs = pair_off_host[27];
+  SFX_REQUIRE(pair_off_host[0] == 0 && pairs >= 0 && pairs <= 26ll * n && pair_off_host[14] == pair_off_host[13],
+              "sfx_subm_conv_wgrad: pair offsets are not those of lists without the centre offset");
+  for (int k = 0; k < 27; ++k)
+    SFX_REQUIRE(pair_off_host[k + 1] >= pair_off_host[k], "sfx_subm_conv_wgrad: pair offsets decrease");
+  SFX_REQUIRE(pairs == 0 || (pair_in && pair_out && fits(pairs, 1)), "sfx_subm_conv_wgrad: null pair lists");
+  // reduction splits: about two workgroups per CU over the whole launch, every offset cut at the same chunk, so
+  // an offset gets ceil(pairs / chunk) work items -- none when it has no pairs
+  const int tiles = (int)(sfx::ceil_div(cout, WG2_T) * sfx::ceil_div(cin, WG2_T));
+  const long long total = (long long)n + pairs;
+  const long long want = sfx::ceil_div(2 * num_cus(), tiles);
+  SubmWgradPlan plan;
+  plan.chunk = (int)sfx::ceil_div(sfx::ceil_div(total, want), BK) * BK;
+  plan.item_off[0] = 0;
+  for (int k = 0; k < 27; ++k) {
+    plan.pair_off[k] = pair_off_host[k];
+    const int count = k == 13 ? n : pair_off_host[k + 1] - pair_off_host[k];
+    plan.item_off[k + 1] = plan.item_off[k] + (int)sfx::ceil_div(count, plan.chunk);
+  }
+  plan.pair_off[27] = pairs;
+  hipStream_t st = sfx::as_stream(stream);
+  const dim3 grid(tiles, plan.item_off[27]);
+  if (g_prec == 1)
+    subm_wgrad_kernel<2><<<grid, 256, 0, st>>>(n, cin, cout, dy, ldy, x, ldx, nbr, pair_in, pair_out, plan, dw, ldw, db);
+  else
+    subm_wgrad_kernel<3><<<grid, 256, 0, st>>>(n, cin, cout, dy, ldy, x, ldx, nbr, pair_in, pair_out, plan, dw, ldw, db);
+  return sfx::check_launch("sfx_subm_conv_wgrad");
 }
 
 int sfx_transpose(int rows, int cols, const float* src, long long lds, float* dst, long long ldd, void* stream) {

@@ -279,6 +279,68 @@ __global__ void __launch_bounds__(256) colsum2_final_kernel(int C, int blocks, c
   if (lane == 0) out[j] = s;
 }
 
+// ---- LayerNorm affine gradient: (sum_m dY, sum_m dY * xhat) per column, xhat recomputed from X ------------
+// A wave owns a row at a time (lane l holds columns l, l + 64, ..: C <= 512), recomputes the row's mean and
+// biased variance, and keeps fp64 column partials in registers over its rows of the 128-row block; the four
+// waves' partials are added in wave order and written as one partial row of the colsum2 layout, which
+// colsum2_final_kernel reduces in its fixed order: the result does not depend on scheduling.
+constexpr int LNW_MAXV = 8;
+
+__global__ void __launch_bounds__(256) ln_wgrad_kernel(int M, int C, const float* __restrict__ X, long long ldx,
+                                                       const float* __restrict__ dY, long long ldgy, float eps,
+                                                       double* __restrict__ part) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int m0 = blockIdx.x * COL_BLOCK_ROWS, m1 = min(M, m0 + COL_BLOCK_ROWS);
+  double sb[LNW_MAXV], sg[LNW_MAXV];
+#pragma unroll
+  for (int i = 0; i < LNW_MAXV; ++i) sb[i] = sg[i] = 0.0;
+  const float inv_c = 1.f / (float)C;
+  for (int m = m0 + w; m < m1; m += 4) {
+    float x[LNW_MAXV], g[LNW_MAXV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < LNW_MAXV; ++i) {
+      const int c = lane + 64 * i;
+      x[i] = c < C ? X[(long long)m * ldx + c] : 0.f;
+      g[i] = c < C ? dY[(long long)m * ldgy + c] : 0.f;
+      s += x[i];
+    }
+    const float mean = sfx::wave_sum(s) * inv_c;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < LNW_MAXV; ++i) {
+      const float d = lane + 64 * i < C ? x[i] - mean : 0.f;
+      q += d * d;
+    }
+    const float rstd = 1.f / sqrtf(sfx::wave_sum(q) * inv_c + eps);
+#pragma unroll
+    for (int i = 0; i < LNW_MAXV; ++i) {
+      sb[i] += g[i];
+      sg[i] += (double)g[i] * (double)((x[i] - mean) * rstd);
+    }
+  }
+  __shared__ double red[2][4][64 * LNW_MAXV];
+#pragma unroll
+  for (int i = 0; i < LNW_MAXV; ++i) {
+    red[0][w][lane + 64 * i] = sb[i];
+    red[1][w][lane + 64 * i] = sg[i];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    part[(long long)blockIdx.x * 2 * C + c] = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
+    part[(long long)blockIdx.x * 2 * C + C + c] = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
+  }
+}
+
+// sums = (dbeta, dgamma) in fp64 -> the fp32 gradients, stored or added
+__global__ void ln_wgrad_store_kernel(int C, const double* __restrict__ sums, float* __restrict__ dgamma,
+                                      float* __restrict__ dbeta, int accumulate) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)sums[c];
+  if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)sums[C + c];
+}
+
 // mean, biased var -> rstd; scale = gamma*rstd, shift = beta - mean*scale; running stats (unbiased var)
 __global__ void bn_finalize_kernel(int C, double count, const double* __restrict__ sums, const float* __restrict__ gamma,
                                    const float* __restrict__ beta, float eps, float momentum,
@@ -517,6 +579,27 @@ static int colsum2(int mode, int M, int C, const float* X, long long ldx, const 
                                                                       dY, ldgy, static_cast<double*>(ws));
   colsum2_final_kernel<<<sfx::ceil_div(2 * C, 4), 256, 0, st>>>(C, blocks, static_cast<double*>(ws), sums);
   return sfx::check_launch(what);
+}
+
+size_t sfx_layernorm_wgrad_workspace_bytes(int M, int C) {
+  return sfx_colsum2_workspace_bytes(M, C) + 2 * (size_t)(C > 0 ? C : 0) * sizeof(double);
+}
+
+int sfx_layernorm_wgrad(int M, int C, const float* X, long long ldx, const float* dY, long long ldgy, float eps,
+                        void* ws, size_t ws_bytes, float* dgamma, float* dbeta, int accumulate, void* stream) {
+  SFX_REQUIRE(M >= 0 && C > 0 && C <= 64 * LNW_MAXV, "sfx_layernorm_wgrad: C must be in [1, 512]");
+  if (M == 0) return SFX_OK;
+  SFX_REQUIRE(X && dY && (dgamma || dbeta), "sfx_layernorm_wgrad: null buffer");
+  SFX_REQUIRE(ldx >= C && ldgy >= C, "sfx_layernorm_wgrad: leading dim");
+  SFX_REQUIRE(ws && ws_bytes >= sfx_layernorm_wgrad_workspace_bytes(M, C), "sfx_layernorm_wgrad: workspace too small");
+  hipStream_t st = sfx::as_stream(stream);
+  const int blocks = (int)sfx::ceil_div(M, COL_BLOCK_ROWS);
+  double* part = static_cast<double*>(ws);
+  double* sums = part + (size_t)blocks * 2 * C;
+  ln_wgrad_kernel<<<blocks, 256, 0, st>>>(M, C, X, ldx, dY, ldgy, eps, part);
+  colsum2_final_kernel<<<sfx::ceil_div(2 * C, 4), 256, 0, st>>>(C, blocks, part, sums);
+  ln_wgrad_store_kernel<<<sfx::ceil_div(C, 256), 256, 0, st>>>(C, sums, dgamma, dbeta, accumulate);
+  return sfx::check_launch("sfx_layernorm_wgrad");
 }
 
 int sfx_bn_stats(int M, int C, const float* X, long long ldx, void* ws, size_t ws_bytes, double* sums,

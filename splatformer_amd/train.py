@@ -7,8 +7,9 @@ image L1 loss `sum_v |pred_v - gt_v|.mean() / num_images / len(batch)` (train.py
 the LPIPS term needs VGG weights that are not available offline and is left out), backward through the
 renderer to the packed refined record, then the hand-written refiner backward.  Every `accumulate_step`
 micro-steps: gradient all-reduce (DDP average, one flat bucket over RCCL), clip_grad_norm_(2.0) and
-Adam(lr 3e-5, eps 1e-15) on the trainable parameters (attn.qkv, utils/optimizers.py:48-52,
-configs/train/default.gin).
+Adam(lr 3e-5, eps 1e-15) on the trainable parameters (by default attn.qkv, utils/optimizers.py:48-52,
+configs/train/default.gin; Trainer(finetune_list=...) selects any other set, None all of them, with a learning
+rate per parameter group as the reference's lr_dict).
 """
 from __future__ import annotations
 
@@ -54,15 +55,54 @@ def refine_train(fp: FeaturePredictor, gs: Dict[str, Tensor], masks, perms=None,
     n_tanh = fp.ch["means"] if fp.output_features[0] == "means" else 0
     o = torch.empty(n, out_dim, device=dev, dtype=torch.float32)
     packed = ops.linear(hs[-1], wl, bl, act=ops.ACT_TANH, act_ncols=n_tanh, residual=feat, pre_out=o)
-    return packed, dict(bb=bb_tape, hs=hs, o=o, n_tanh=n_tanh, cb=cb)
+    # the heads' first-layer input is kept only when a head trains (its weight gradient reads it)
+    return packed, dict(bb=bb_tape, hs=hs, o=o, n_tanh=n_tanh, cb=cb,
+                        x=x if pt.trains(fp.features_outputhead) else None)
+
+
+def scatter_head_grads(fp: FeaturePredictor, dw1: Tensor, db1: Tensor, dmids, dwl: Tensor, dbl: Tensor) -> None:
+    """Add the gradients of the packed head matrices (FeaturePredictor._packed_heads: w1 [G*W, kpad] / b1, per mid
+    layer (wm [G, W, W], bm [G, W]), the block-structured last layer wl [out_dim, G*W] / bl) to .grad of the
+    per-feature features_outputhead[f] parameters that require grad: head g's row block of w1 without the pad
+    columns, wm[g], and its own rows and hidden units of the last layer."""
+    W = fp.width
+    r = 0
+    for g, f in enumerate(fp.output_features):
+        head = fp.features_outputhead[f]
+        c = fp.ch[f]
+        sl = slice(g * W, (g + 1) * W)
+        pieces = [(head[0].weight, dw1[sl, :fp.head_in]), (head[0].bias, db1[sl])]
+        for li, (dwm, dbm) in enumerate(dmids):
+            pieces += [(head[2 * (li + 1)].weight, dwm[g]), (head[2 * (li + 1)].bias, dbm[g])]
+        pieces += [(head[-1].weight, dwl[r:r + c, sl]), (head[-1].bias, dbl[r:r + c])]
+        for p, grad in pieces:
+            if p.requires_grad:
+                if p.grad is None:
+                    p.grad = torch.zeros_like(p)
+                p.grad += grad
+        r += c
 
 
 def refine_backward(fp: FeaturePredictor, tape: dict, d_packed: Tensor) -> None:
-    """d(loss)/d(packed record) -> qkv gradients (heads and the input attributes are not trained)."""
+    """d(loss)/d(packed record) -> gradients of every refiner parameter that requires grad (the input attributes
+    are not trained)."""
     w1, b1, mids, wl, bl, out_dim = fp._packed_heads()
     G, W = len(fp.output_features), fp.width
     hs = tape["hs"]
-    dz = tops.act_bwd(d_packed.contiguous(), tape["o"], tops.DACT_TANH_OUT, ncols=tape["n_tanh"])
+    heads = tape.get("x") is not None
+    dev = d_packed.device
+    n = d_packed.shape[0]
+    if heads:  # the last layer's weight gradient wants a multiple of 4 output columns: dz in zero-padded rows
+        npad = (out_dim + 3) // 4 * 4
+        dzp = torch.zeros(n, npad, device=dev, dtype=torch.float32)
+        dz = tops.act_bwd(d_packed.contiguous(), tape["o"], tops.DACT_TANH_OUT, ncols=tape["n_tanh"],
+                          out=dzp[:, :out_dim])
+        dwl = torch.zeros(npad, G * W, device=dev, dtype=torch.float32)
+        dbl = torch.zeros(npad, device=dev, dtype=torch.float32)
+        tops.linear_wgrad(dzp, hs[-1], dwl, dbl)
+        dmids = [(torch.zeros_like(wm), torch.zeros_like(bm)) for wm, bm in mids]
+    else:
+        dz = tops.act_bwd(d_packed.contiguous(), tape["o"], tops.DACT_TANH_OUT, ncols=tape["n_tanh"])
     dh = tops.linear_bwd_data(dz, pt.wt(wl), dact=tops.DACT_RELU, dact_pre=hs[-1])
     for li in reversed(range(len(mids))):
         wm = mids[li][0]
@@ -70,8 +110,15 @@ def refine_backward(fp: FeaturePredictor, tape: dict, d_packed: Tensor) -> None:
         dprev = torch.empty_like(prev)
         for g in range(G):
             sl = slice(g * W, (g + 1) * W)
+            if heads:
+                tops.linear_wgrad(dh[:, sl], prev[:, sl], dmids[li][0][g], dmids[li][1][g])
             tops.linear_bwd_data(dh[:, sl], pt.wt(wm[g]), dact=tops.DACT_RELU, dact_pre=prev[:, sl], out=dprev[:, sl])
         dh = dprev
+    if heads:
+        dw1 = torch.zeros_like(w1)
+        db1 = torch.zeros_like(b1)
+        tops.linear_wgrad(dh, tape["x"], dw1, db1)
+        scatter_head_grads(fp, dw1, db1, dmids, dwl, dbl)
     dx = tops.linear_bwd_data(dh, pt.wt(w1))
     pt.backbone_backward(tape["bb"], dx[:, :tape["cb"]].contiguous())
 
@@ -98,13 +145,47 @@ def image_l1(pred: Sequence[Tensor], gt: Sequence[Tensor]) -> Tensor:
 
 
 # ---- optimiser ------------------------------------------------------------------------------------------------
-class Trainer:
-    """FeaturePredictor training on libsfx: filter_grads(['attn.qkv']), flat gradient bucket (one RCCL
-    all-reduce per optimiser step under DDP), clip_grad_norm_ + Adam on device."""
+def select_trainable(model: torch.nn.Module, finetune_list) -> None:
+    """utils/optimizers.py:4-16 filter_grads: a parameter requires grad iff its name contains one of the substrings;
+    None or an empty list selects every parameter."""
+    names = tuple(finetune_list or ())
+    for name, p in model.named_parameters():
+        p.requires_grad_(not names or any(s in name for s in names))
 
-    def __init__(self, model: FeaturePredictor, lr: float = 3e-5, eps: float = 1e-15, betas=(0.9, 0.999),
+
+def param_lrs(model: FeaturePredictor, lr) -> Dict[int, float]:
+    """id(parameter) -> learning rate.  `lr` is one number, or the reference's lr_dict
+    (utils/optimizers.py:49-54, configs/train/default.gin): 'backbone' for every backbone parameter, one optional
+    key per head feature ('means', 'scales', ...), 'base' for whatever has no key of its own."""
+    if not isinstance(lr, dict):
+        return {id(p): float(lr) for p in model.parameters()}
+    if "base" not in lr:
+        raise ValueError("an lr dict needs a 'base' entry (the fallback of utils/optimizers.py)")
+    out = {id(p): float(lr["base"]) for p in model.parameters()}
+    for p in model.backbone.parameters():
+        out[id(p)] = float(lr.get("backbone", lr["base"]))
+    for f, head in model.features_outputhead.items():
+        for p in head.parameters():
+            out[id(p)] = float(lr.get(f, lr["base"]))
+    return out
+
+
+class Trainer:
+    """FeaturePredictor training on libsfx: filter_grads(finetune_list), flat gradient bucket (one RCCL
+    all-reduce per optimiser step under DDP), clip_grad_norm_ + Adam on device.
+
+    finetune_list: substrings of parameter names, with the semantics of the reference's filter_grads -- a
+    parameter trains iff its name contains one of them.  The default ("attn.qkv",) is the reference's fine-tuning
+    recipe (utils/optimizers.py:46-47); None or () trains every parameter (training from scratch), and any other
+    list works too, e.g. ("mlp.fc", "features_outputhead").  The backward computes the gradients of exactly the
+    selected parameters; a block whose mlp.fc1 / fc2 train runs the unfused MLP branch.
+    lr: one learning rate, or a dict in the shape of the reference's lr_dict: 'backbone', one key per head feature
+    ('means', 'scales', 'opacities', 'quats', 'features_dc', 'features_rest') and 'base' as the fallback; applied
+    per parameter in optimizer_step."""
+
+    def __init__(self, model: FeaturePredictor, lr=3e-5, eps: float = 1e-15, betas=(0.9, 0.999),
                  grad_clip_norm: float = 2.0, accumulate_step: int = 1, group=None, generator=None,
-                 precision: Optional[str] = None, render: Optional[str] = None):
+                 precision: Optional[str] = None, render: Optional[str] = None, finetune_list=("attn.qkv",)):
         """precision: "fp32" (default; fp32-accurate refiner forward + backward) or "amp", the reference's
         `training.enable_amp` (train.py:214-299, configs/train/default.gin:11): refiner forward and backward in
         the autocast precision class (ptv3_ops.precision); the renderer, loss and optimiser stay fp32 as in the
@@ -123,10 +204,16 @@ class Trainer:
         self.precision = precision or os.environ.get("SFX_TRAIN_PREC", "fp32")
         if self.precision not in ops.PRECISIONS:
             raise ValueError(f"precision {self.precision!r}: expected one of {sorted(ops.PRECISIONS)}")
-        for name, p in model.named_parameters():       # utils/optimizers.py:4-16, :48-52
-            p.requires_grad_("attn.qkv" in name)
+        if isinstance(finetune_list, str):
+            finetune_list = (finetune_list,)
+        self.finetune_list = tuple(finetune_list or ())
+        select_trainable(model, self.finetune_list)    # utils/optimizers.py:4-16, :48-52
         pt.check_trainable(model.backbone.backbone)
         self.params = [p for p in model.parameters() if p.requires_grad]
+        if not self.params:
+            raise ValueError(f"finetune_list {self.finetune_list!r} selects no parameter")
+        lrs = param_lrs(model, lr)
+        self.param_lr = [lrs[id(p)] for p in self.params]
         dev = self.params[0].device
         total = sum(p.numel() for p in self.params)
         self.flat_grad = torch.zeros(total, device=dev, dtype=torch.float32)
@@ -195,11 +282,12 @@ class Trainer:
                 self.micro = 0
                 return
         self.step_count += 1
-        for p, m1, m2 in zip(self.params, self.exp_avg, self.exp_avg_sq):
-            tops.adam_step(p.data, p.grad, m1, m2, self.step_count, self.lr, self.betas, self.eps, grad_scale=coef)
+        for p, m1, m2, lr in zip(self.params, self.exp_avg, self.exp_avg_sq, self.param_lr):
+            tops.adam_step(p.data, p.grad, m1, m2, self.step_count, lr, self.betas, self.eps, grad_scale=coef)
             # adam_step writes through a raw pointer, which torch does not see: bump the parameter's version so
             # every cache keyed on it (fp16x2 pre-split ops.weight_split, W^T ptv3_train.wt) is rebuilt
-            torch.autograd.graph.increment_version(p)
+            if lr != 0.0:  # (lr 0: the moments move, the parameter keeps its bits)
+                torch.autograd.graph.increment_version(p)
         self.flat_grad.zero_()
         self.micro = 0
 
@@ -212,6 +300,11 @@ class Trainer:
                 "masks": self.masks.state_dict() if hasattr(self.masks, "state_dict") else None}
 
     def load_state_dict(self, sd: dict) -> None:
+        """The moments follow self.params, i.e. the finetune_list the state was saved with."""
+        shapes = [tuple(t.shape) for t in sd["exp_avg"]]
+        if shapes != [tuple(p.shape) for p in self.params]:
+            raise ValueError("optimiser state does not match the trainable parameters (saved with another "
+                             "finetune_list?)")
         for dst, src in zip(self.exp_avg + self.exp_avg_sq, list(sd["exp_avg"]) + list(sd["exp_avg_sq"])):
             dst.copy_(src)
         self.step_count = int(sd["step_count"])

@@ -57,6 +57,63 @@ def linear_wgrad(dy: Tensor, x: Tensor, dw: Tensor, db: Optional[Tensor]) -> Non
     call("sfx_linear_wgrad", M, N, K, pd, ldd, px, ldx, pw, ldw, ptr(db), stream())
 
 
+def linear_wgrad_rs(dy: Tensor, x: Tensor, rowscale: Optional[Tensor], dw: Tensor, db: Optional[Tensor]) -> None:
+    """dW += (rowscale o dY)^T X ; db += colsum(rowscale o dY)  (rowscale None: linear_wgrad)."""
+    M, N = dy.shape
+    K = x.shape[1]
+    pd, ldd = _rows(dy)
+    px, ldx = _rows(x)
+    pw, ldw = _rows(dw)
+    scaled = None if rowscale is None else torch.empty(M, N, device=dy.device, dtype=torch.float32)
+    call("sfx_linear_wgrad_rs", M, N, K, pd, ldd, px, ldx, ptr(rowscale), ptr(scaled), pw, ldw, ptr(db), stream())
+
+
+def linear_wgrad_padk(dy: Tensor, x: Tensor, dw: Tensor, db: Optional[Tensor]) -> None:
+    """linear_wgrad for an input whose width K is no multiple of 4 (the embedding's Cin = 23 / 59): the gradient
+    against K rounded up to 4 goes to a weight-sized scratch and its first K columns are added to dW.  Where `x`
+    is a 16-byte-aligned column view of wider rows (the feat view of the refiner's zero-padded head input) the
+    extra columns are read in place (their products land in the scratch columns that are dropped); otherwise
+    `x` is copied to zero-padded rows."""
+    M, K = x.shape
+    kp = (K + 3) // 4 * 4
+    if kp == K and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0:
+        return linear_wgrad(dy, x, dw, db)
+    ld = x.stride(0)
+    col0 = x.storage_offset() % ld if ld > 0 else 0
+    if x.stride(1) == 1 and ld % 4 == 0 and x.data_ptr() % 16 == 0 and col0 + kp <= ld and \
+            x.storage_offset() + (M - 1) * ld + kp <= x.untyped_storage().nbytes() // 4:
+        xp = torch.as_strided(x, (M, kp), (ld, 1), x.storage_offset())
+    else:
+        xp = torch.nn.functional.pad(x, (0, kp - K))
+    scratch = torch.zeros(dy.shape[1], kp, device=dy.device, dtype=torch.float32)
+    linear_wgrad(dy, xp, scratch, db)
+    dw += scratch[:, :K]
+
+
+def subm_conv_wgrad(dy: Tensor, x: Tensor, smap, dw: Tensor, db: Optional[Tensor]) -> None:
+    """dW [Cout, 27*Cin] += SubMConv3d weight gradient of (dy, conv input x); db += colsum(dy) (accumulating)."""
+    n, cout = dy.shape
+    cin = x.shape[1]
+    if dw.shape != (cout, 27 * cin) or not dw.is_contiguous():
+        raise ValueError("subm_conv_wgrad: dw must be a contiguous [Cout, 27*Cin] tensor")
+    pd, ldd = _rows(dy)
+    px, ldx = _rows(x)
+    call("sfx_subm_conv_wgrad", n, cin, cout, pd, ldd, px, ldx, ptr(smap.nbr), ptr(smap.pair_in), ptr(smap.pair_out),
+         smap._off_host, ptr(dw), 27 * cin, ptr(db), stream())
+
+
+def layernorm_wgrad(x: Tensor, dy: Tensor, eps: float, dgamma: Optional[Tensor], dbeta: Optional[Tensor],
+                    accumulate: bool = True) -> None:
+    """dgamma (+)= sum_m dy * xhat(x), dbeta (+)= sum_m dy  (deterministic fp64 two-level reduction)."""
+    M, Cc = x.shape
+    nbytes = int(_lib.fn("sfx_layernorm_wgrad_workspace_bytes")(max(M, 1), Cc))
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    px, ldx = _rows(x)
+    pd, ldd = _rows(dy)
+    call("sfx_layernorm_wgrad", M, Cc, px, ldx, pd, ldd, float(eps), ws.data_ptr(), nbytes, ptr(dgamma), ptr(dbeta),
+         1 if accumulate else 0, stream())
+
+
 def subm_conv_bwd_data(dy: Tensor, smap, weight_t: Tensor, dx: Tensor) -> Tensor:
     """dx += SubMConv3d^T(dy) (accumulating)."""
     n, cout = dy.shape
@@ -203,9 +260,21 @@ def bn_apply(st: BNState, act: int, residual: Optional[Tensor] = None, residual_
     return out
 
 
+def gelu(x: Tensor) -> Tensor:
+    """GELU(x) (sfx_affine_act with unit scale): the MLP hidden activation recomputed from the stored fc1 output."""
+    M, Cc = x.shape
+    one = torch.ones(Cc, device=x.device, dtype=torch.float32)
+    zero = torch.zeros(Cc, device=x.device, dtype=torch.float32)
+    out = torch.empty(M, Cc, device=x.device, dtype=torch.float32)
+    px, ldx = _rows(x)
+    call("sfx_affine_act", M, Cc, px, ldx, ptr(one), ptr(zero), 1, None, 0, None, ptr(out), Cc, stream())
+    return out
+
+
 def bn_act_bwd(st: BNState, bn: torch.nn.BatchNorm1d, act: int, dy: Tensor, out: Optional[Tensor] = None,
-               accumulate: bool = False, group=None) -> Tensor:
-    """d x of act(BN_train(x)) given dy (SyncBatchNorm sums all-reduced when `group` is set)."""
+               accumulate: bool = False, group=None, local_sums=None) -> Tensor:
+    """d x of act(BN_train(x)) given dy (SyncBatchNorm sums all-reduced when `group` is set).  `local_sums(sums)` is
+    called with this rank's (sum g, sum g*xhat) before the all-reduce (the affine parameters' gradients)."""
     x = st.x
     M, Cc = x.shape
     dev = x.device
@@ -216,6 +285,8 @@ def bn_act_bwd(st: BNState, bn: torch.nn.BatchNorm1d, act: int, dy: Tensor, out:
     g, b = bn.weight.detach(), bn.bias.detach()
     call("sfx_bn_act_bwd_reduce", M, Cc, px, ldx, ptr(st.mean), ptr(st.rstd), ptr(g), ptr(b), act, pd, ldd,
          ws.data_ptr(), nbytes, sums.data_ptr(), stream())
+    if local_sums is not None:
+        local_sums(sums)
     _allreduce(sums, group)
     if out is None:
         assert not accumulate
