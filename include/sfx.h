@@ -631,8 +631,10 @@ int sfx_fps(int n, int m, const float* xyz, int start, int* out, float* dist_ws,
  *   Linear / LayerNorm layouts, contiguous) -> `stream` (sfx_mlp_stream_floats(C) floats: the pre-split weights
  *   in the kernel's LDS-DMA slab order) and `params` (sfx_mlp_params_floats(C) floats); workspace: 9C ints.
  * sfx_block_mlp: X [M][ldx], Y [M][ldy] (distinct buffers), 16-byte aligned rows; eps = the LayerNorm eps.
- * At C >= 128 (and in the training entries below) a launch whose last round of workgroups is at most half full
- * runs that round as hidden-chunk partials + a fixed-order combine (bitwise reproducible) in a library-owned
+ * At C >= 128 the entry picks per launch, from M and the CU count, whole tiles (128 points per workgroup) or
+ * hidden-split tiles (64 points, a wave pair per 32; SFX_MLP_HS=0 / 1 force one); the two differ in the order of
+ * two fc2 partial sums.  There (and in the training entries below) a launch whose last round of workgroups is
+ * thin enough runs that round as hidden-chunk partials + a fixed-order combine (bitwise reproducible) in a library-owned
  * scratch buffer per (device, stream), reused in stream order (SFX_MLP_SPLIT=0: one launch).  The buffer grows
  * on the first call that needs more (synchronising that stream once): under HIP graph capture, run the entry
  * once at the captured sizes before capturing. */
@@ -644,6 +646,12 @@ int sfx_block_mlp(int M, int C, const float* x, long long ldx, const float* stre
                   float* y, long long ldy, int* rowexp, void* stream_);
 /* (ABI v13) rowexp (optional, [M] int32): also writes sfx_subm_rowexp(y) -- the next Block's fused SubM conv input
  * exponents -- from the output rows it just computed */
+/* (ABI 16, additive) The launch plan of the calling host thread's latest sfx_block_mlp that launched (tests assert
+ * which path ran): *kind 0 = whole tiles (a wave per 32 points), 1 = hidden split (a wave pair per 32 points), -1
+ * before the thread's first call; *pts = points per workgroup; *main_wgs workgroups cover rows [0, main_wgs * pts)
+ * in one unsplit launch; *tail_wgs workgroups of points cover the remaining rows, each as *split hidden-chunk
+ * partials (*split = 1 and *tail_wgs = 0: no split tail).  NULL pointers are skipped.  Returns SFX_OK. */
+int sfx_block_mlp_last_plan(int* kind, int* split, int* main_wgs, int* tail_wgs, int* pts);
 /* (ABI v13) training forward of the same tail (train.py:240-289, model.train()): also stores z [M][4C] (contiguous)
  * = fc1(LN2(x)), the pre-activation the backward needs, and applies the DropPath keep factor rowscale [M] (NULL:
  * none) to the branch: y = x + rowscale * (fc2(GELU(z)) + b2). */

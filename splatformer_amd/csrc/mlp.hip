@@ -604,9 +604,10 @@ int run_impl(int M, const float* x, long long ldx, const float* stream, const fl
                                                                                   : "sfx_block_mlp_bwd");
 }
 
-// The C = 256 eval tail split: one 4-wave workgroup per CU (512-register waves), so a launch of W workgroups runs
-// ceil(W / CUs) rounds; when the last round is at most half full its workgroups run as SPLIT = 2 or 4 hidden-chunk
-// splits (one round of 1/SPLIT the work) + mlp_combine_kernel.  Scratch: one buffer per (device, stream) behind a
+// The tail split: a launch of W workgroups over `slots` resident ones (C = 256: one 4-wave workgroup of 512-register
+// waves per CU, else two) runs ceil(W / slots) rounds; when the last round is at most half full its workgroups run as
+// SPLIT hidden-chunk splits (one round of 1/SPLIT the work) + mlp_combine_kernel: 4 / 3 / 2 for hidden-split tiles,
+// 8 / 4 / 2 for the whole tiles of C >= 128 (eval).  Scratch: one buffer per (device, stream) behind a
 // mutex (as sfx::lookback_state), grown on demand -- launches on two streams or host threads never share partials,
 // and a stream's reuse is ordered by the stream itself.  Growing synchronises that stream before freeing the old
 // buffer (work in flight may still read it), so it must not happen inside a graph capture: warm the entry up once
@@ -645,25 +646,53 @@ int cu_count() {
   return cus;
 }
 
-template <int C, int WAVES, int RING, bool HS, int KIND = MLP_EVAL, bool ONE = false>
-int run_split(int M, const float* x, long long ldx, const float* stream, const float* par, float eps, float* y,
-              long long ldy, hipStream_t st, const float* rowscale, float* z) {
-  constexpr int PTS = HS ? WAVES * 16 : WAVES * 32;  // points per workgroup
-  constexpr int NCH = C / 16;                       // hidden chunks
-  const int wgs = (M + PTS - 1) / PTS, slots = ((WAVES == 4 && C > 128) ? 1 : 2) * cu_count();
-  const int full = wgs / slots * slots, r = wgs - full;
+// sfx_block_mlp_last_plan: what the calling thread's latest eval call launched (set once its launches succeeded)
+struct MlpPlan {
+  int kind = -1, split = 1, main_wgs = 0, tail_wgs = 0, pts = 0;
+};
+thread_local MlpPlan last_plan;
+
+// whether a tail of (hidden-split / whole) tiles at C may run as S hidden-chunk splits: whole chunks per split;
+// hidden-split tiles 4 / 3 / 2; whole tiles 8 / 4 / 2 at C >= 128 only (the 128-point launches of C <= 96 measured
+// no gain: their rounds are short and the combine is not free)
+constexpr bool split_ok(bool hs, int C, int S) {
+  if ((C / 16) % S != 0) return false;
+  if (hs) return S == 4 || S == 3 || S == 2;
+  return C >= 128 && (S == 8 || S == 4 || S == 2);
+}
+
+// the split of a launch's last round: the largest factor whose pieces fit one round (r workgroups left over after
+// `full` whole rounds' worth); 1 = unsplit (no whole round before it, no tail, SFX_MLP_SPLIT=0, or none fits).
+// Hidden-split tiles: a round of `slots` pieces.  Whole tiles: one piece per CU, also at C = 128 where two fit --
+// a piece alone on its CU runs faster than two sharing it (MI355X, C = 128, after one whole round: a 64-workgroup
+// tail +24 us as 256 pieces, +28 as 512; config B's 38-workgroup tail 103 us per call as 152 pieces, 105-110 as
+// 304: profiles/r09_mlp_rounds.txt).
+int tail_split(bool hs, int C, int full, int r, int slots) {
   static int mode = -1;
   if (mode < 0) {
     const char* e = getenv("SFX_MLP_SPLIT");
     mode = (e && *e) ? atoi(e) : 1;
   }
-  int S = 1;
-  // (the 128-point non-HS launches of C <= 96 measured no gain: their rounds are short and the combine is not free)
-  if (HS && mode && full > 0 && r > 0) {
-    for (int cand : {4, 3, 2})
-      if (NCH % cand == 0 && cand * r <= slots) { S = cand; break; }
-  }
-  if (S == 1) return run_impl<C, WAVES, RING, HS, KIND, ONE>(M, x, ldx, stream, par, eps, y, ldy, st, rowscale, z);
+  if (!mode || full <= 0 || r <= 0) return 1;
+  const int room = hs ? slots : cu_count();
+  for (int cand : {8, 4, 3, 2})
+    if (split_ok(hs, C, cand) && cand * r <= room) return cand;
+  return 1;
+}
+
+template <int C, int WAVES, int RING, bool HS, int KIND = MLP_EVAL, bool ONE = false>
+int run_split(int M, const float* x, long long ldx, const float* stream, const float* par, float eps, float* y,
+              long long ldy, hipStream_t st, const float* rowscale, float* z) {
+  constexpr int PTS = HS ? WAVES * 16 : WAVES * 32;  // points per workgroup
+  const int wgs = (M + PTS - 1) / PTS, slots = ((WAVES == 4 && C > 128) ? 1 : 2) * cu_count();
+  const int full = wgs / slots * slots, r = wgs - full;
+  const int S = tail_split(HS, C, full, r, slots);
+  auto ran = [&](int rc) {  // records the plan of an eval call whose launches succeeded
+    if (KIND == MLP_EVAL && rc == SFX_OK) last_plan = MlpPlan{HS, S, S > 1 ? full : wgs, S > 1 ? r : 0, PTS};
+    return rc;
+  };
+  if (S == 1)
+    return ran(run_impl<C, WAVES, RING, HS, KIND, ONE>(M, x, ldx, stream, par, eps, y, ldy, st, rowscale, z));
   const int M1 = full * PTS, Mt = M - M1;
   float* P = mlp_split_scratch((size_t)S * Mt * C, st);
   SFX_REQUIRE(P, "sfx_block_mlp: tail scratch allocation failed");
@@ -683,11 +712,12 @@ int run_split(int M, const float* x, long long ldx, const float* stream, const f
     mlp_combine_kernel<SS><<<(unsigned)((Mt + 3) / 4), 256, 0, st>>>(Mt, C, KIND == MLP_BWD ? nullptr : xt, ldx, P, \
                                                                      yt, ldy, et);                               \
   } while (0)
-  if constexpr (NCH % 4 == 0) { if (S == 4) SFX_MLP_SPLIT_LAUNCH(4); }
-  if constexpr (NCH % 3 == 0) { if (S == 3) SFX_MLP_SPLIT_LAUNCH(3); }
-  if constexpr (NCH % 2 == 0) { if (S == 2) SFX_MLP_SPLIT_LAUNCH(2); }
+  if constexpr (split_ok(HS, C, 8)) { if (S == 8) SFX_MLP_SPLIT_LAUNCH(8); }
+  if constexpr (split_ok(HS, C, 4)) { if (S == 4) SFX_MLP_SPLIT_LAUNCH(4); }
+  if constexpr (split_ok(HS, C, 3)) { if (S == 3) SFX_MLP_SPLIT_LAUNCH(3); }
+  if constexpr (split_ok(HS, C, 2)) { if (S == 2) SFX_MLP_SPLIT_LAUNCH(2); }
 #undef SFX_MLP_SPLIT_LAUNCH
-  return sfx::check_launch("sfx_block_mlp (split tail)");
+  return ran(sfx::check_launch("sfx_block_mlp (split tail)"));
 }
 
 template <int C, int WAVES, int RING, bool HS>
@@ -695,6 +725,61 @@ int run_eval_split(int M, const float* x, long long ldx, const float* stream, co
                    long long ldy, hipStream_t st, int* rowexp) {
   return run_split<C, WAVES, RING, HS>(M, x, ldx, stream, par, eps, y, ldy, st, nullptr,
                                        reinterpret_cast<float*>(rowexp));
+}
+
+// an eval launch that never splits its tail (the 256-point workgroups, the forced hidden split of C <= 96)
+template <int C, int WAVES, int RING, bool HS = false>
+int run_eval_one(int M, const float* x, long long ldx, const float* stream, const float* par, float eps, float* y,
+                 long long ldy, hipStream_t st, int* rowexp) {
+  constexpr int PTS = HS ? WAVES * 16 : WAVES * 32;
+  const int rc = run_impl<C, WAVES, RING, HS>(M, x, ldx, stream, par, eps, y, ldy, st, nullptr,
+                                              reinterpret_cast<float*>(rowexp));
+  if (rc == SFX_OK) last_plan = MlpPlan{HS, 1, (M + PTS - 1) / PTS, 0, PTS};
+  return rc;
+}
+
+// ---- the launch plan of the eval entry at C = 128 and 256 -------------------------------------------------------
+// Both tile kinds stream the whole weight image (8 C^2 floats) through every workgroup's LDS ring; a whole tile
+// covers 128 points with it, a hidden-split tile 64, so whole tiles move half the L2 -> LDS bytes per point, but a
+// launch runs whole rounds of `slots` workgroups and a thin last round still costs most of one.  The plan prices
+// both kinds for the launch's M -- a fixed part, the whole rounds, and the last round either unsplit or as
+// tail_split()'s pieces + the combine -- and runs the cheaper one.  Constants: microseconds per call on MI355X
+// (256 CUs, tools/mlp_bench.py, profiles/r09_mlp_rounds.txt):
+//   rounds   C = 256 whole 165.0 / 310.1 us for 1 / 2 rounds, hidden-split 96.4 / 177.5 / 251.8 for 1 / 2 / 3;
+//            C = 128 whole 77.7 / 139.7 / 202.6, hidden-split 50.5 / 87.8 / 127.1 / 160.1 for 1 .. 4;
+//   unsplit last round at most half full: 0.5 - 0.8 of a round (C = 256: whole 39 of 256 workgroups 114 us,
+//            hidden-split 78 of 256 55 us; C = 128: whole 38 of 512 38 us, hidden-split 76 of 512 19 us);
+//   split tails, tail kernel + the 5 us combine together: whole tiles C = 256 8-way 23 - 34 us, 4-way 36 - 44;
+//            C = 128 8-way 10 (1 workgroup), 4-way 15 - 24, 2-way 40: about 1.1 R / SPLIT + 5; hidden-split tiles
+//            cost more of their round, C = 128 4-way 25, 2-way 43 (1.9 R / SPLIT + 5: two pieces share a CU),
+//            C = 256 2-way 54 (1.25).  Each piece factor rests on one or two shapes (1.9: M = 70349 and 81920).
+// Only the ratios between the two kinds' prices decide.  The constants were fitted on 256 CUs and are used as they
+// are for another CU count: the rounds of a launch are counted from the device's own slots, so the choice stays a
+// valid launch either way, only less well tuned.
+struct MlpCost {
+  float fw, rw, pw;  // whole tiles: fixed part of a call, one round, a split piece's factor on round / SPLIT
+  float fh, rh, ph;  // hidden-split tiles
+  float thin;        // an unsplit last round at most half full, as a share of a round
+};
+constexpr MlpCost COST128 = {15.f, 62.5f, 1.1f, 14.f, 37.f, 1.9f, 0.6f};
+constexpr MlpCost COST256 = {20.f, 145.f, 1.1f, 18.f, 78.f, 1.25f, 0.75f};
+constexpr float COST_COMBINE = 5.f;
+
+float plan_cost(const MlpCost& k, bool hs, int C, int M, int slots) {
+  const int pts = hs ? 64 : 128, wgs = (M + pts - 1) / pts;
+  const int full = wgs / slots * slots, r = wgs - full;
+  const int S = tail_split(hs, C, full, r, slots);
+  const float R = hs ? k.rh : k.rw;
+  float t = (hs ? k.fh : k.fw) + (float)(full / slots) * R;
+  if (r > 0) t += S > 1 ? (hs ? k.ph : k.pw) * R / (float)S + COST_COMBINE : (2 * r <= slots ? k.thin * R : R);
+  return t;
+}
+
+// true: hidden-split tiles (ties keep them)
+bool plan_hs(int C, int M) {
+  const MlpCost& k = C == 128 ? COST128 : COST256;
+  const int slots = (C > 128 ? 1 : 2) * cu_count();
+  return plan_cost(k, true, C, M, slots) <= plan_cost(k, false, C, M, slots);
 }
 
 // the training kinds run the default eval geometry of each C (4 waves; hidden split at C = 128, 256, and for the
@@ -773,27 +858,36 @@ int sfx_block_mlp(int M, int C, const float* x, long long ldx, const float* stre
   hipStream_t st = sfx::as_stream(stream_);
   // C <= 128: 4-wave (128-point) workgroups, two per CU -- measured 1.0-1.2x faster than one 8-wave workgroup
   // (profiles/r04_mlp_waves_hs.txt); SFX_MLP_WAVES=8 restores the 256-point workgroups.  Hidden split (a wave pair
-  // per 32 points): SFX_MLP_HS=1 (default) at C = 128 and 256, where it measured faster (108.8 -> 100.0 /
-  // 239.7 -> 220.6 us); 2 at every C; 0 nowhere.  Both read per call (tests switch them).
+  // per 32 points): SFX_MLP_HS=1 at C = 128 and 256; 2 at every C; 0 nowhere; unset: at C <= 96 nowhere, at C = 128
+  // and 256 what plan_hs() prices cheaper for this M.  Both read per call (tests switch them).
   const char* e = getenv("SFX_MLP_WAVES");
   const int waves = (e && *e) ? atoi(e) : 4;
   const char* f = getenv("SFX_MLP_HS");
-  const int hs = (f && *f) ? atoi(f) : 1;
+  const int hs = (f && *f) ? atoi(f) : ((C >= 128 && waves == 4) ? (int)plan_hs(C, M) : 1);
   switch (C) {
     // (waves, ring phases): 4 waves = 128 points per workgroup, 2 workgroups per CU for C <= 128 (64 KB ring);
-    // C = 256 runs 4 waves as 2 hidden-split pairs (its LN2 fragments + output accumulators fill 512 registers)
-    case 64: return waves == 4 ? (hs == 2 ? run_impl<64, 4, 4, true>(M, x, ldx, stream, params, eps, y, ldy, st, nullptr, reinterpret_cast<float*>(rowexp))
+    // C = 256: one workgroup per CU (its LN2 fragments + output accumulators fill 512 registers)
+    case 64: return waves == 4 ? (hs == 2 ? run_eval_one<64, 4, 4, true>(M, x, ldx, stream, params, eps, y, ldy, st, rowexp)
                                           : run_eval_split<64, 4, 4, false>(M, x, ldx, stream, params, eps, y, ldy, st, rowexp))
-                               : run_impl<64, 8, 4>(M, x, ldx, stream, params, eps, y, ldy, st, nullptr, reinterpret_cast<float*>(rowexp));
-    case 96: return waves == 4 ? (hs == 2 ? run_impl<96, 4, 4, true>(M, x, ldx, stream, params, eps, y, ldy, st, nullptr, reinterpret_cast<float*>(rowexp))
+                               : run_eval_one<64, 8, 4>(M, x, ldx, stream, params, eps, y, ldy, st, rowexp);
+    case 96: return waves == 4 ? (hs == 2 ? run_eval_one<96, 4, 4, true>(M, x, ldx, stream, params, eps, y, ldy, st, rowexp)
                                           : run_eval_split<96, 4, 4, false>(M, x, ldx, stream, params, eps, y, ldy, st, rowexp))
-                               : run_impl<96, 8, 4>(M, x, ldx, stream, params, eps, y, ldy, st, nullptr, reinterpret_cast<float*>(rowexp));
+                               : run_eval_one<96, 8, 4>(M, x, ldx, stream, params, eps, y, ldy, st, rowexp);
     case 128: return waves == 4 ? (hs >= 1 ? run_eval_split<128, 4, 4, true>(M, x, ldx, stream, params, eps, y, ldy, st, rowexp)
-                                          : run_impl<128, 4, 4>(M, x, ldx, stream, params, eps, y, ldy, st, nullptr, reinterpret_cast<float*>(rowexp)))
-                                : run_impl<128, 8, 4>(M, x, ldx, stream, params, eps, y, ldy, st, nullptr, reinterpret_cast<float*>(rowexp));
+                                          : run_eval_split<128, 4, 4, false>(M, x, ldx, stream, params, eps, y, ldy, st, rowexp))
+                                : run_eval_one<128, 8, 4>(M, x, ldx, stream, params, eps, y, ldy, st, rowexp);
     default: return hs ? run_eval_split<256, 4, SFX_MLP_RING256, true>(M, x, ldx, stream, params, eps, y, ldy, st, rowexp)
-                       : run_impl<256, 4, SFX_MLP_RING256>(M, x, ldx, stream, params, eps, y, ldy, st, nullptr, reinterpret_cast<float*>(rowexp));
+                       : run_eval_split<256, 4, SFX_MLP_RING256, false>(M, x, ldx, stream, params, eps, y, ldy, st, rowexp);
   }
+}
+
+int sfx_block_mlp_last_plan(int* kind, int* split, int* main_wgs, int* tail_wgs, int* pts) {
+  if (kind) *kind = last_plan.kind;
+  if (split) *split = last_plan.split;
+  if (main_wgs) *main_wgs = last_plan.main_wgs;
+  if (tail_wgs) *tail_wgs = last_plan.tail_wgs;
+  if (pts) *pts = last_plan.pts;
+  return SFX_OK;
 }
 
 // (ABI v13) training forward: as sfx_block_mlp, plus z [M, 4C] (contiguous) = the pre-activation fc1(LN2(x)) and

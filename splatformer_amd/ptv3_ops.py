@@ -328,6 +328,15 @@ def block_mlp(x2: Tensor, ln2, fc1, fc2, out: Optional[Tensor] = None, rowexp: O
     return out
 
 
+def block_mlp_last_plan() -> dict:
+    """Launch plan of this thread's latest block_mlp (sfx_block_mlp_last_plan): kind 0 whole tiles / 1 hidden split
+    (-1 before the first call), split, main_wgs, tail_wgs, pts (points per workgroup)."""
+    import ctypes
+    v = [ctypes.c_int(0) for _ in range(5)]
+    call("sfx_block_mlp_last_plan", *[ctypes.addressof(c) for c in v])
+    return dict(zip(("kind", "split", "main_wgs", "tail_wgs", "pts"), (c.value for c in v)))
+
+
 def block_mlp_train(x2: Tensor, ln2, fc1, fc2, z: Tensor, rowscale: Optional[Tensor] = None,
                     out: Optional[Tensor] = None) -> Tensor:
     """Training forward of the Block MLP tail in one launch (csrc/mlp.hip MLP_TRAIN): Y = x2 + rowscale *
