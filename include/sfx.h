@@ -260,7 +260,9 @@ int sfx_window_attention_bwd(int num_windows, int window, int heads, int head_di
 int sfx_window_attention_varlen_bwd(int num_windows, int max_window, int heads, int head_dim, int channels,
                                     const float* qkv, const int* order, const int* win3, float scale,
                                     const float* dout, float* dqkv, float* stats, void* stream);
-/* nn.LayerNorm backward w.r.t. the input: dX = LN'(X) dY (+ dR) */
+/* nn.LayerNorm backward w.r.t. the input: dX = LN'(X) dY (+ dR); C <= 512; every leading dimension (ldr when dR is
+ * given) >= C.  16-byte-aligned operands with leading dimensions that are multiples of 4 take the float4 kernels at
+ * C = 64 / 96 / 128 / 256 / 512, anything else the one-wave-per-row kernel. */
 int sfx_layernorm_bwd(int M, int C, const float* X, long long ldx, const float* gamma, const float* dY,
                       long long ldgy, const float* dR, long long ldr, float eps, float* dX, long long lddx,
                       void* stream);
@@ -275,7 +277,10 @@ int sfx_layernorm_wgrad(int M, int C, const float* X, long long ldx, const float
 int sfx_cpe_ln_bwd(int M, int C, const float* U, const float* X1, const float* gamma_cpe, const float* gamma1,
                    const float* dX2, const float* dH, float eps, float* dX1, float* dU, void* stream);
 /* train-mode nn.BatchNorm1d(eps 1e-3, momentum 0.01) [+ GELU]; SyncBatchNorm: all-reduce `sums` between the
- * reduce and the finalize/apply calls.  sums = double[2C]. */
+ * reduce and the finalize/apply calls.  sums = double[2C]; `count` = the global row count the sums cover;
+ * running_mean / running_var may both be NULL (no update).  Every leading dimension >= C (ldr when R is given;
+ * R is read at row ridx[m], or row m when ridx is NULL).  The two reductions are deterministic (fp64 partials
+ * added in a fixed order). */
 size_t sfx_colsum2_workspace_bytes(int M, int C);
 int sfx_bn_stats(int M, int C, const float* X, long long ldx, void* ws, size_t ws_bytes, double* sums, void* stream);
 int sfx_bn_finalize(int C, double count, const double* sums, const float* gamma, const float* beta, float eps,
@@ -289,14 +294,18 @@ int sfx_bn_act_bwd_reduce(int M, int C, const float* X, long long ldx, const flo
 int sfx_bn_act_bwd_apply(int M, int C, const float* X, long long ldx, const float* mean, const float* rstd,
                          const float* gamma, const float* beta, int act, const float* dY, long long ldgy,
                          const double* sums, double count, float* dX, long long lddx, int accumulate, void* stream);
-/* SerializedPooling segment_csr(max) with arg-max (train) and its backward (dX rows pre-zeroed) */
+/* SerializedPooling segment_csr(max) with arg-max (train) and its backward (dX rows pre-zeroed).  arg = the FIRST
+ * row in run order that holds the maximum (a later row wins only when strictly greater: ties, duplicate rows and
+ * +-0.0 keep the earlier one), -1 and Y = -inf for an empty run; the backward writes dY to that row only. */
 int sfx_segment_max_arg(int m, int C, const int* idx_ptr, const int* sorted_idx, const float* X, float* Y, int* arg,
                         void* stream);
 int sfx_segment_max_bwd(int m, int C, const float* dY, const int* arg, float* dX, void* stream);
-/* SerializedUnpooling backward of feat[inverse]: Y[s] = sum of the rows of cluster s */
+/* SerializedUnpooling backward of feat[inverse]: Y[s] = sum of the rows of cluster s (fp64 accumulation in run
+ * order); ldx >= C, Y rows contiguous */
 int sfx_segment_sum(int m, int C, const int* idx_ptr, const int* sorted_idx, const float* X, long long ldx, float* Y,
                     void* stream);
-/* dX = dY * act'(pre) on cols < ncols (1 GELU pre-act, 2 ReLU, 3 tanh given its output) */
+/* dX = dY * act'(pre) on cols < ncols (1 GELU pre-act, 2 ReLU, 3 tanh given its output), dX = dY on the others;
+ * every leading dimension >= N */
 int sfx_act_bwd(int M, int N, const float* dY, long long ldgy, const float* pre, long long ldp, int act, int ncols,
                 float* dX, long long lddx, void* stream);
 /* (ABI v13) DropPath keep mask of n points (timm DropPath, pointtransformer_v3.py:145): out[i] = 1/keep or 0,

@@ -434,15 +434,17 @@ __global__ void __launch_bounds__(256) segment_max_bwd_kernel(int m, int C, cons
   if (r >= 0) dX[(long long)r * C + c] = dY[e];
 }
 
-// Y[s] = sum of X rows of run s (backward of the unpooling gather feat[inverse])
+// Y[s] = sum of X rows of run s (backward of the unpooling gather feat[inverse]), accumulated in fp64 in run
+// order: an fp32 running sum over a 1000-row run with rows 1e-3 .. 1e3 apart was 1.8e-6 off (rel. L2 to fp64,
+// tests/test_gpu_train_kernels.py, C = 1); the loop is bound by the row gathers, not by the adds
 __global__ void segment_sum_kernel(int m, int C, const int* __restrict__ idx_ptr, const int* __restrict__ sidx,
                                    const float* __restrict__ X, long long ldx, float* __restrict__ Y) {
   const int s = blockIdx.x;
   const int beg = idx_ptr[s], end = idx_ptr[s + 1];
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    float v = 0.f;
-    for (int p = beg; p < end; ++p) v += X[(long long)sidx[p] * ldx + c];
-    Y[(long long)s * C + c] = v;
+    double v = 0.0;
+    for (int p = beg; p < end; ++p) v += (double)X[(long long)sidx[p] * ldx + c];
+    Y[(long long)s * C + c] = (float)v;
   }
 }
 
@@ -526,6 +528,7 @@ int sfx_layernorm_bwd(int M, int C, const float* X, long long ldx, const float* 
   SFX_REQUIRE(M >= 0 && C > 0 && C <= 64 * MAXV, "sfx_layernorm_bwd: C must be in [1, 512]");
   if (M == 0) return SFX_OK;
   SFX_REQUIRE(X && gamma && dY && dX, "sfx_layernorm_bwd: null buffer");
+  SFX_REQUIRE(ldx >= C && ldgy >= C && lddx >= C && (!dR || ldr >= C), "sfx_layernorm_bwd: leading dim");
   hipStream_t st = sfx::as_stream(stream);
   const bool v4 = al16(X) && al16(gamma) && al16(dY) && al16(dX) && (!dR || al16(dR)) && ldx % 4 == 0 &&
                   ldgy % 4 == 0 && lddx % 4 == 0 && (!dR || ldr % 4 == 0);
@@ -605,6 +608,7 @@ int sfx_layernorm_wgrad(int M, int C, const float* X, long long ldx, const float
 int sfx_bn_stats(int M, int C, const float* X, long long ldx, void* ws, size_t ws_bytes, double* sums,
                  void* stream) {
   SFX_REQUIRE(X && sums, "sfx_bn_stats: null buffer");
+  SFX_REQUIRE(ldx >= C, "sfx_bn_stats: leading dim");
   return colsum2(0, M, C, X, ldx, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, ws, ws_bytes, sums,
                  sfx::as_stream(stream), "sfx_bn_stats");
 }
@@ -626,6 +630,7 @@ int sfx_affine_act(int M, int C, const float* X, long long ldx, const float* sca
   SFX_REQUIRE(M >= 0 && C > 0 && (act == 0 || act == 1), "sfx_affine_act: bad args");
   if (M == 0) return SFX_OK;
   SFX_REQUIRE(X && scale && shift && Y, "sfx_affine_act: null buffer");
+  SFX_REQUIRE(ldx >= C && ldy >= C && (!R || ldr >= C), "sfx_affine_act: leading dim");
   affine_act_kernel<<<sfx::ceil_div((long long)M * C, 256), 256, 0, sfx::as_stream(stream)>>>(
       M, C, X, ldx, scale, shift, act, R, ldr, ridx, Y, ldy);
   return sfx::check_launch("sfx_affine_act");
@@ -636,6 +641,7 @@ int sfx_bn_act_bwd_reduce(int M, int C, const float* X, long long ldx, const flo
                           size_t ws_bytes, double* sums, void* stream) {
   SFX_REQUIRE(X && mean && rstd && gamma && beta && dY && sums, "sfx_bn_act_bwd_reduce: null buffer");
   SFX_REQUIRE(act == 0 || act == 1, "sfx_bn_act_bwd_reduce: bad act");
+  SFX_REQUIRE(ldx >= C && ldgy >= C, "sfx_bn_act_bwd_reduce: leading dim");
   return colsum2(1, M, C, X, ldx, mean, rstd, gamma, beta, act, dY, ldgy, ws, ws_bytes, sums, sfx::as_stream(stream),
                  "sfx_bn_act_bwd_reduce");
 }
@@ -646,6 +652,7 @@ int sfx_bn_act_bwd_apply(int M, int C, const float* X, long long ldx, const floa
   SFX_REQUIRE(M >= 0 && C > 0 && count >= 1.0 && (act == 0 || act == 1), "sfx_bn_act_bwd_apply: bad args");
   if (M == 0) return SFX_OK;
   SFX_REQUIRE(X && mean && rstd && gamma && beta && dY && sums && dX, "sfx_bn_act_bwd_apply: null buffer");
+  SFX_REQUIRE(ldx >= C && ldgy >= C && lddx >= C, "sfx_bn_act_bwd_apply: leading dim");
   bn_act_bwd_apply_kernel<<<sfx::ceil_div((long long)M * C, 256), 256, 0, sfx::as_stream(stream)>>>(
       M, C, X, ldx, mean, rstd, gamma, beta, act, dY, ldgy, sums, count, dX, lddx, accumulate);
   return sfx::check_launch("sfx_bn_act_bwd_apply");
@@ -674,6 +681,7 @@ int sfx_segment_sum(int m, int C, const int* idx_ptr, const int* sorted_idx, con
   SFX_REQUIRE(m >= 0 && C > 0, "sfx_segment_sum: bad args");
   if (m == 0) return SFX_OK;
   SFX_REQUIRE(idx_ptr && sorted_idx && X && Y, "sfx_segment_sum: null buffer");
+  SFX_REQUIRE(ldx >= C, "sfx_segment_sum: leading dim");
   const int threads = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
   segment_sum_kernel<<<m, threads, 0, sfx::as_stream(stream)>>>(m, C, idx_ptr, sorted_idx, X, ldx, Y);
   return sfx::check_launch("sfx_segment_sum");
@@ -684,6 +692,7 @@ int sfx_act_bwd(int M, int N, const float* dY, long long ldgy, const float* pre,
   SFX_REQUIRE(M >= 0 && N > 0 && act >= 1 && act <= 3, "sfx_act_bwd: bad args");
   if (M == 0) return SFX_OK;
   SFX_REQUIRE(dY && pre && dX, "sfx_act_bwd: null buffer");
+  SFX_REQUIRE(ldgy >= N && ldp >= N && lddx >= N, "sfx_act_bwd: leading dim");
   act_bwd_kernel<<<sfx::ceil_div((long long)M * N, 256), 256, 0, sfx::as_stream(stream)>>>(M, N, dY, ldgy, pre, ldp,
                                                                                            act, ncols, dX, lddx);
   return sfx::check_launch("sfx_act_bwd");
