@@ -67,17 +67,30 @@ int sfx_sort_pairs_u64(long long n, const uint64_t* keys_in, const int32_t* vals
 /* gsplat.spherical_harmonics(degrees_to_use, viewdirs[N,3], coeffs[N,K,3]) -> colors[N,3]  (gs_utils.py:78) */
 int sfx_sh_fwd(int n, int num_bases, int degrees_to_use, const float* viewdirs, const float* coeffs, float* colors,
                void* stream);
+/* v_coeffs[N,K,3]: every element is written; rows k >= (degrees_to_use + 1)^2 get exactly zero */
 int sfx_sh_bwd(int n, int num_bases, int degrees_to_use, const float* viewdirs, const float* v_colors,
                float* v_coeffs, void* stream);
 
 /* gsplat.project_gaussians(means3d, scales, glob_scale, quats(w,x,y,z), viewmat[3x4 row-major], fx, fy, cx, cy,
  *                          img_height, img_width, block_width, clip_thresh)  (gs_utils.py:82-95)
- * -> xys[N,2], depths[N], radii[N], conics[N,3], compensation[N], num_tiles_hit[N], cov3d[N,6] */
+ * -> xys[N,2], depths[N], radii[N], conics[N,3], compensation[N], num_tiles_hit[N], cov3d[N,6]
+ * Every element of every output is written.  A Gaussian that is culled (tz <= clip_thresh, zero determinant, or a
+ * tile box of area 0) has radii = num_tiles_hit = 0 and xys = depths = compensation = 0; as in gsplat, cov3d is
+ * stored once the near-plane test passes and conics once the determinant test passes, so a Gaussian culled later
+ * keeps them.  Non-finite quaternions (NaN, zero, or a norm whose square underflows in fp32, e.g. 1e-30): the
+ * rotation, hence the radius, is NaN; the tile box's float -> int conversions turn NaN into 0, the area is 0
+ * and the Gaussian is culled -- radii, num_tiles_hit, xys, depths and compensation are 0 and nothing downstream
+ * touches it (no intersection is emitted, sfx_project_bwd skips it); its conics and cov3d are NaN.  The eval and
+ * training preps never get there: they normalise quaternions first and substitute the identity for NaN. */
 int sfx_project_fwd(int n, const float* means, const float* scales, float glob_scale, const float* quats,
                     const float* viewmat, float fx, float fy, float cx, float cy, int img_h, int img_w,
                     int block_width, float clip_thresh, float* xys, float* depths, int* radii, float* conics,
                     float* compensation, int* num_tiles_hit, float* cov3d, void* stream);
-/* autograd backward of project_gaussians; v_cov2d / v_cov3d optional */
+/* autograd backward of project_gaussians (gsplat's project_gaussians_backward_kernel: no frustum clamp in the EWA
+ * vjp, v_quat with respect to the normalised quaternion with its radial part kept, 0.5 / (compensation + 1e-6));
+ * v_cov2d [N,3] / v_cov3d [N,6] optional, off-diagonal entries summed.  Every element of every output is written.
+ * Rows with radii <= 0 get exactly zero in all five outputs; for those rows the kernel reads only radii -- their
+ * cov3d, conics, compensation and upstream gradients may hold anything, NaN included. */
 int sfx_project_bwd(int n, const float* means, const float* scales, float glob_scale, const float* quats,
                     const float* viewmat, float fx, float fy, const float* cov3d, const int* radii,
                     const float* conics, const float* compensation, const float* v_xy, const float* v_depth,

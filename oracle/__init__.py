@@ -16,6 +16,10 @@ Contents (each function cites the reference file:line it restates):
                     models/pointtransformer_v3.py, plus the FeaturePredictor
                     heads of models/feature_predictor.py.
   * render_ref   -- utils/gs_utils.py:29-114 render glue.
+  * render_grad_ref / render_cases -- plain differentiable forwards of the
+                    render operators (fp64 autograd pins gsplat_ref's hand-written
+                    backward restatements) and the seeded edge cases both test
+                    files of the render backward share.
 
 Parity status: the glue (gs_utils.py, feature_predictor.py) is pinned by
 golden vectors captured from the reference itself (tests/golden/).  The

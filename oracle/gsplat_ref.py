@@ -44,13 +44,18 @@ def num_sh_bases(degree: int) -> int:
     return (degree + 1) ** 2
 
 
-def _sh_basis(degree: int, d: torch.Tensor) -> list:
+def _sqrt(x: torch.Tensor) -> torch.Tensor:
+    """sqrt_rn for float32 (bit-stable), torch.sqrt for any other dtype."""
+    return sqrt_rn(x) if x.dtype == f32 else torch.sqrt(x)
+
+
+def _sh_basis(degree: int, d: torch.Tensor, dtype: torch.dtype = f32) -> list:
     """Real SH basis (gsplat sh.cu sh_coeffs_to_color), dirs re-normalised."""
     n = d.shape[0]
-    b = [torch.full((n,), SH_C0, dtype=f32)]
+    b = [torch.full((n,), SH_C0, dtype=dtype)]
     if degree < 1:
         return b
-    nrm = sqrt_rn(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
+    nrm = _sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
     x, y, z = d[:, 0] / nrm, d[:, 1] / nrm, d[:, 2] / nrm
     b += [-SH_C1 * y, SH_C1 * z, -SH_C1 * x]
     if degree < 2:
@@ -83,12 +88,13 @@ def spherical_harmonics(degrees_to_use: int, viewdirs: torch.Tensor, coeffs: tor
 
 
 def spherical_harmonics_bwd(degrees_to_use: int, viewdirs: torch.Tensor, v_colors: torch.Tensor,
-                            num_bases: int) -> torch.Tensor:
-    """compute_sh_backward_kernel: v_coeffs[:,k,:] = basis_k * v_colors (0 above degrees_to_use)."""
-    b = _sh_basis(degrees_to_use, viewdirs.to(f32))
-    out = torch.zeros(v_colors.shape[0], num_bases, 3, dtype=f32)
+                            num_bases: int, dtype: torch.dtype = f32) -> torch.Tensor:
+    """compute_sh_backward_kernel: v_coeffs[:,k,:] = basis_k * v_colors (0 above degrees_to_use).  `dtype`: the
+    arithmetic's precision (float64: the same formula on the same fp32 inputs, for error bars)."""
+    b = _sh_basis(degrees_to_use, viewdirs.to(dtype), dtype)
+    out = torch.zeros(v_colors.shape[0], num_bases, 3, dtype=dtype)
     for k in range(len(b)):
-        out[:, k, :] = b[k][:, None] * v_colors
+        out[:, k, :] = b[k][:, None] * v_colors.to(dtype)
     return out
 
 
@@ -96,7 +102,7 @@ def quat_to_rotmat(q: torch.Tensor) -> torch.Tensor:
     """helpers.cuh quat_to_rotmat: q = (w,x,y,z) scaled by s = 1/sqrt(w^2+x^2+y^2+z^2) (gsplat: rsqrtf; the
     canonical form here is the correctly rounded 1/sqrt, sum left to right); returns R[N,3,3] row-major."""
     ss = ((q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2]) + q[:, 3] * q[:, 3]
-    s = 1.0 / sqrt_rn(ss)
+    s = 1.0 / _sqrt(ss)
     w, x, y, z = q[:, 0] * s, q[:, 1] * s, q[:, 2] * s, q[:, 3] * s
     R = torch.stack([
         1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
@@ -105,14 +111,22 @@ def quat_to_rotmat(q: torch.Tensor) -> torch.Tensor:
     return R
 
 
+def cvt_i32(x: torch.Tensor) -> torch.Tensor:
+    """The GPU's float -> int32 conversion (gsplat's cvt.rzi.s32.f32, gfx950's v_cvt_i32_f32): truncation toward
+    zero, saturating at the int32 range, NaN -> 0.  torch's CPU cast gives INT_MIN for all three of NaN, +inf and
+    values past the range, which would make the oracle's tile box of a non-finite radius machine-dependent."""
+    x = torch.nan_to_num(x.to(f32), nan=0.0, posinf=3e38, neginf=-3e38)
+    return x.clamp(min=-2147483648.0, max=2147483520.0).to(torch.int32) + (x >= 2147483648.0).to(torch.int32) * 127
+
+
 def tile_bbox(xy: torch.Tensor, radius: torch.Tensor, tiles_x: int, tiles_y: int, bw: int):
     """helpers.cuh get_tile_bbox/get_bbox: (int) truncation toward zero, clamp to [0, tiles]."""
     tcx, tcy = xy[:, 0] / float(bw), xy[:, 1] / float(bw)
     tr = radius.to(f32) / float(bw)
-    x0 = (tcx - tr).to(torch.int32).clamp(min=0).clamp(max=tiles_x)
-    x1 = (tcx + tr + 1).to(torch.int32).clamp(min=0).clamp(max=tiles_x)
-    y0 = (tcy - tr).to(torch.int32).clamp(min=0).clamp(max=tiles_y)
-    y1 = (tcy + tr + 1).to(torch.int32).clamp(min=0).clamp(max=tiles_y)
+    x0 = cvt_i32(tcx - tr).clamp(min=0).clamp(max=tiles_x)
+    x1 = cvt_i32(tcx + tr + 1).clamp(min=0).clamp(max=tiles_x)
+    y0 = cvt_i32(tcy - tr).clamp(min=0).clamp(max=tiles_y)
+    y1 = cvt_i32(tcy + tr + 1).clamp(min=0).clamp(max=tiles_y)
     return x0, y0, x1, y1
 
 
@@ -183,13 +197,17 @@ def project_gaussians(means3d, scales, glob_scale, quats, viewmat, fx, fy, cx, c
     xys = torch.stack([tx * rw * fx + cx, ty * rw * fy + cy], -1)
     tiles_x = (img_width + block_width - 1) // block_width
     tiles_y = (img_height + block_width - 1) // block_width
-    x0, y0, x1, y1 = tile_bbox(xys, torch.nan_to_num(radius, nan=0.0, posinf=0.0), tiles_x, tiles_y, block_width)
+    # Non-finite radius (a zero, denormal-norm or NaN quaternion gives a NaN rotation, so a NaN radius): the tile
+    # box goes through the kernel's float -> int conversions (cvt_i32: NaN -> 0), all four corners are 0, the area
+    # is 0 and the Gaussian is culled like any other that misses the image -- radii, num_tiles_hit, xys, depths
+    # and compensation are 0; conics and cov3d, which gsplat stores before the area test, keep their NaNs.
+    x0, y0, x1, y1 = tile_bbox(xys, radius, tiles_x, tiles_y, block_width)
     area = (x1 - x0) * (y1 - y0)
     vis = ok & (area > 0)
     z2 = lambda t: torch.where(vis.reshape(-1, *([1] * (t.dim() - 1))), t, torch.zeros_like(t))
     out_conics = torch.where(ok[:, None], conics, torch.zeros_like(conics))
     out_cov3d = torch.where(keep[:, None], cov3d, torch.zeros_like(cov3d))
-    return (z2(xys), z2(tz), z2(radius).to(torch.int32), out_conics, z2(comp), z2(area).to(torch.int32), out_cov3d)
+    return (z2(xys), z2(tz), cvt_i32(z2(radius)), out_conics, z2(comp), z2(area).to(torch.int32), out_cov3d)
 
 
 def map_gaussian_to_intersects(xys, depths, radii, cum_tiles_hit, tiles_x, tiles_y, block_width):
@@ -319,17 +337,25 @@ def rasterize_gaussians(xys, depths, radii, conics, num_tiles_hit, colors, opaci
 
 
 def rasterize_backward(tiles_x, tiles_y, bw, H, W, gids_sorted, tile_bins, xys, conics, colors, opacity,
-                       background, final_Ts, final_idx, v_out, v_out_alpha):
-    """rasterize_backward_kernel: back-to-front replay from final_idx (alpha clamp 0.99).
+                       background, final_Ts, final_idx, v_out, v_out_alpha, dtype: torch.dtype = f32,
+                       return_abs: bool = False, alpha_clamp: float = 0.99):
+    """rasterize_backward_kernel: back-to-front replay from final_idx (alpha clamp 0.99: gsplat's backward
+    constant, which differs from the forward's 0.999 on purpose; `alpha_clamp` exists so a test can show that the
+    other value misses the bars).
 
-    Returns (v_xy[N,2], v_conic[N,3], v_rgb[N,3], v_opacity[N,1])."""
+    Returns (v_xy[N,2], v_conic[N,3], v_rgb[N,3], v_opacity[N,1]); with return_abs also v_xy_abs[N,2], the sum of
+    the per-pixel |v_xy| (gsplat's absgrad).  `dtype`: the arithmetic's precision (float64: the same formula on
+    the same fp32 inputs and forward state, for error bars)."""
     n = xys.shape[0]
-    v_xy = torch.zeros(n, 2, dtype=f32)
-    v_conic = torch.zeros(n, 3, dtype=f32)
-    v_rgb = torch.zeros(n, 3, dtype=f32)
-    v_op = torch.zeros(n, dtype=f32)
-    op = opacity.reshape(-1).to(f32)
-    bg = background.to(f32)
+    v_xy = torch.zeros(n, 2, dtype=dtype)
+    v_xy_abs = torch.zeros(n, 2, dtype=dtype)
+    v_conic = torch.zeros(n, 3, dtype=dtype)
+    v_rgb = torch.zeros(n, 3, dtype=dtype)
+    v_op = torch.zeros(n, dtype=dtype)
+    xys, conics, colors = xys.to(dtype), conics.to(dtype), colors.to(dtype)
+    final_Ts, v_out, v_out_alpha = final_Ts.to(dtype), v_out.to(dtype), v_out_alpha.to(dtype)
+    op = opacity.reshape(-1).to(dtype)
+    bg = background.to(dtype)
     for ty in range(tiles_y):
         for tx in range(tiles_x):
             t = ty * tiles_x + tx
@@ -340,7 +366,7 @@ def rasterize_backward(tiles_x, tiles_y, bw, H, W, gids_sorted, tile_bins, xys, 
             if not bool(inside.any()):
                 continue
             px, py = px[inside], py[inside]
-            pxf, pyf = px.to(f32) + 0.5, py.to(f32) + 0.5
+            pxf, pyf = px.to(dtype) + 0.5, py.to(dtype) + 0.5
             Tf = final_Ts[py, px]
             bfin = final_idx[py, px].long()
             vo = v_out[py, px]
@@ -353,14 +379,14 @@ def rasterize_backward(tiles_x, tiles_y, bw, H, W, gids_sorted, tile_bins, xys, 
             con = conics[g]
             sigma = 0.5 * (con[:, 0][None] * dx * dx + con[:, 2][None] * dy * dy) + con[:, 1][None] * dx * dy
             vis = torch.exp(-sigma)
-            alpha = torch.clamp(op[g][None] * vis, max=0.99)
+            alpha = torch.clamp(op[g][None] * vis, max=alpha_clamp)
             valid = (pos <= bfin[:, None]) & ~((sigma < 0) | (alpha < 1.0 / 255.0))
             a = torch.where(valid, alpha, torch.zeros_like(alpha))
             ra = 1.0 / (1.0 - a)
             # back-to-front: T_j = T_final * prod_{k>=j} ra_k (sequential, reversed)
             Tj = Tf[:, None] * torch.flip(torch.cumprod(torch.flip(ra, [1]), 1), [1])
             fac = a * Tj
-            c = colors[g].to(f32)  # [m,3]
+            c = colors[g]  # [m,3]
             contrib = fac[:, :, None] * c[None]  # [P,m,3]
             # buffer_j = sum_{k>j} contrib_k  (accumulated back to front)
             rc = torch.flip(torch.cumsum(torch.flip(contrib, [1]), 1), [1])
@@ -369,29 +395,40 @@ def rasterize_backward(tiles_x, tiles_y, bw, H, W, gids_sorted, tile_bins, xys, 
             v_alpha = v_alpha + Tf[:, None] * ra * voa[:, None]
             v_alpha = v_alpha - (Tf[:, None] * ra)[:, :, None].mul(bg[None, None] * vo[:, None, :]).sum(-1)
             v_sigma = -op[g][None] * vis * v_alpha
-            w = valid.to(f32)
-            g_rgb = (fac[:, :, None] * vo[:, None, :] * w[:, :, None]).sum(0)
+            # invalid pairs add nothing (selected, not multiplied by 0: exp(-sigma) overflows where sigma << 0)
+            w3 = valid[:, :, None]
+            keep = lambda t: torch.where(w3 if t.dim() == 3 else valid, t, torch.zeros_like(t))
+            g_rgb = keep(fac[:, :, None] * vo[:, None, :]).sum(0)
             g_con = torch.stack([0.5 * v_sigma * dx * dx, v_sigma * dx * dy, 0.5 * v_sigma * dy * dy], -1)
-            g_con = (g_con * w[:, :, None]).sum(0)
+            g_con = keep(g_con).sum(0)
             g_xy = torch.stack([v_sigma * (con[:, 0][None] * dx + con[:, 1][None] * dy),
                                 v_sigma * (con[:, 1][None] * dx + con[:, 2][None] * dy)], -1)
-            g_xy = (g_xy * w[:, :, None]).sum(0)
-            g_o = (vis * v_alpha * w).sum(0)
+            g_xy = keep(g_xy)
+            g_o = keep(vis * v_alpha).sum(0)
             v_rgb.index_add_(0, g, g_rgb)
             v_conic.index_add_(0, g, g_con)
-            v_xy.index_add_(0, g, g_xy)
+            v_xy.index_add_(0, g, g_xy.sum(0))
+            if return_abs:
+                v_xy_abs.index_add_(0, g, g_xy.abs().sum(0))
             v_op.index_add_(0, g, g_o)
+    if return_abs:
+        return v_xy, v_conic, v_rgb, v_op[:, None], v_xy_abs
     return v_xy, v_conic, v_rgb, v_op[:, None]
 
 
 def project_gaussians_backward(means3d, scales, glob_scale, quats, viewmat, fx, fy, cov3d, radii, conics,
-                               compensation, v_xy, v_depth, v_conic, v_comp):
+                               compensation, v_xy, v_depth, v_conic, v_comp, dtype: torch.dtype = f32,
+                               return_cov: bool = False):
     """project_gaussians_backward_kernel (no frustum clamp in the EWA vjp; quat grad w.r.t. normalised q).
 
-    Returns (v_mean3d[N,3], v_scale[N,3], v_quat[N,4])."""
-    vm = viewmat.reshape(-1)[:12].to(f32)
+    Returns (v_mean3d[N,3], v_scale[N,3], v_quat[N,4]); with return_cov also (v_cov2d[N,3], v_cov3d[N,6]) in
+    gsplat's packing (off-diagonal entries summed).  `dtype`: the arithmetic's precision (float64: the same
+    formula on the same fp32 inputs and forward outputs, for error bars)."""
+    vm = viewmat.reshape(-1)[:12].to(dtype)
     W = vm.reshape(3, 4)[:, :3]
-    p = means3d.to(f32)
+    p = means3d.to(dtype)
+    cov3d, conics, compensation = cov3d.to(dtype), conics.to(dtype), compensation.to(dtype)
+    v_xy, v_depth, v_conic, v_comp = v_xy.to(dtype), v_depth.to(dtype), v_conic.to(dtype), v_comp.to(dtype)
     tx = vm[0] * p[:, 0] + vm[1] * p[:, 1] + vm[2] * p[:, 2] + vm[3]
     ty = vm[4] * p[:, 0] + vm[5] * p[:, 1] + vm[6] * p[:, 2] + vm[7]
     tz = vm[8] * p[:, 0] + vm[9] * p[:, 1] + vm[10] * p[:, 2] + vm[11]
@@ -415,13 +452,13 @@ def project_gaussians_backward(means3d, scales, glob_scale, quats, viewmat, fx, 
     rz = 1.0 / tz
     rz2, rz3 = rz * rz, rz * rz * rz
     n = p.shape[0]
-    J = torch.zeros(n, 3, 3, dtype=f32)
+    J = torch.zeros(n, 3, 3, dtype=dtype)
     J[:, 0, 0] = fx * rz
     J[:, 0, 2] = -fx * tx * rz2
     J[:, 1, 1] = fy * rz
     J[:, 1, 2] = -fy * ty * rz2
     T = J @ W
-    Gc = torch.zeros(n, 3, 3, dtype=f32)
+    Gc = torch.zeros(n, 3, 3, dtype=dtype)
     Gc[:, 0, 0] = vc2[:, 0]
     Gc[:, 0, 1] = 0.5 * vc2[:, 1]
     Gc[:, 1, 0] = 0.5 * vc2[:, 1]
@@ -436,9 +473,9 @@ def project_gaussians_backward(means3d, scales, glob_scale, quats, viewmat, fx, 
                       + 2 * fy * ty * rz3 * vJ[:, 1, 2]], -1)
     v_mean = v_mean + vt @ W
     # scale / rotation
-    q = quats.to(f32)
+    q = quats.to(dtype)
     R = quat_to_rotmat(q)
-    s = glob_scale * scales.to(f32)
+    s = glob_scale * scales.to(dtype)
     vVs = torch.stack([vc3[:, 0], 0.5 * vc3[:, 1], 0.5 * vc3[:, 2], 0.5 * vc3[:, 1], vc3[:, 3], 0.5 * vc3[:, 4],
                        0.5 * vc3[:, 2], 0.5 * vc3[:, 4], vc3[:, 5]], -1).reshape(-1, 3, 3)
     M = R * s[:, None, :]
@@ -459,6 +496,8 @@ def project_gaussians_backward(means3d, scales, glob_scale, quats, viewmat, fx, 
     ], -1)
     live = (radii > 0)[:, None]
     zero = lambda t: torch.where(live, t, torch.zeros_like(t))
+    if return_cov:
+        return zero(v_mean), zero(v_scale), zero(v_quat), zero(vc2), zero(vc3)
     return zero(v_mean), zero(v_scale), zero(v_quat)
 
 
