@@ -630,6 +630,23 @@ int sfx_image_stats_u8(int num_images, long long elems_per_image, const float* p
 size_t sfx_ssim_workspace_bytes(int num_images, int height, int width, int channels);
 int sfx_ssim(int num_images, int height, int width, int channels, const float* img1, const float* img2,
              const float* window, int quantize_u8, float* out, void* ws, size_t ws_bytes, void* stream);
+/* (ABI v16, additive) Training image loss and its derivative: per view v,
+ *   loss_v = l1_weight * mean|p - g| + ssim_weight * (1 - SSIM_v),   means over channels * height * width,
+ * with the SSIM of sfx_ssim (unquantised).  pred / gt: [num_images][height][width][channels] fp32 (HWC).
+ * window: the 11 fp32 taps of the reference's normalised 1-D Gaussian (utils/metrics.py:93-96); the 2-D window is
+ * their outer product, applied separably with fp64 sums.  view_scale: [num_images] on the device, NULL = 1.
+ * terms [num_images][4]: mean|p-g|, SSIM mean, mean (p-g)^2, loss_v (not scaled by view_scale).
+ * d_pred [num_images][height][width][channels] or NULL: view_scale[v] * d loss_v / d pred, written (not
+ * accumulated), sign(0) = 0; it must not overlap pred or gt.  No atomics: the same inputs give the same bits.
+ * ws: 8-byte aligned; sfx_image_loss_workspace_bytes is what a call with d_pred and ssim_weight > 0 needs: the
+ * tile sums, then three fp32 derivative maps (12 bytes per element of pred).  Any other call needs the tile sums
+ * only (the query's size less those 12 bytes per element) and accepts more.
+ * Refused (rc < 0, no launch): sizes < 1, more than 65535 view-channels or 2^40 elements, height above 16 * 65535,
+ * a null buffer, a short or misaligned workspace, a negative weight, d_pred overlapping an input. */
+size_t sfx_image_loss_workspace_bytes(int num_images, int height, int width, int channels);
+int sfx_image_loss(int num_images, int height, int width, int channels, const float* pred, const float* gt,
+                   const float* window, float l1_weight, float ssim_weight, const float* view_scale, float* terms,
+                   float* d_pred, void* ws, size_t ws_bytes, void* stream);
 
 /* Point-cloud downsampling experiments (reference models/pcd_downsampling_methods.py; FeaturePredictor
  * additional_info["downsample"], models/feature_predictor.py:159-196).

@@ -55,11 +55,16 @@ def psnr_u8(pred: torch.Tensor, gt: torch.Tensor, clamp_pred: bool = True) -> to
     return psnr_from_stats(sums, maxes, pred.numel() // max(pred.shape[0], 1))
 
 
-def ssim_window(window_size: int = 11, sigma: float = 1.5) -> torch.Tensor:
-    """The reference's 2-D window (metrics.py:93-101): normalised 1-D Gaussian (fp32), outer product."""
+def gaussian_taps(window_size: int = 11, sigma: float = 1.5) -> torch.Tensor:
+    """The reference's normalised 1-D Gaussian in fp32 (metrics.py:93-96)."""
     g = torch.tensor([math.exp(-(x - window_size // 2) ** 2 / float(2 * sigma ** 2)) for x in range(window_size)],
                      dtype=torch.float32)
-    g = (g / g.sum()).unsqueeze(1)
+    return g / g.sum()
+
+
+def ssim_window(window_size: int = 11, sigma: float = 1.5) -> torch.Tensor:
+    """The reference's 2-D window (metrics.py:93-101): normalised 1-D Gaussian (fp32), outer product."""
+    g = gaussian_taps(window_size, sigma).unsqueeze(1)
     return g.mm(g.t()).float()
 
 

@@ -4,7 +4,8 @@ Per scene: FeaturePredictor forward in train mode (ptv3_train), the refined Gaus
 training views through the gsplat-compatible autograd path (gs_render / gsplat_compat HIP kernels; or, with
 render="batched", through the eval path's single batched pass and its two-launch backward), the
 image L1 loss `sum_v |pred_v - gt_v|.mean() / num_images / len(batch)` (train.py:272-283, image_l1 weight 1;
-the LPIPS term needs VGG weights that are not available offline and is left out), backward through the
+the LPIPS term needs VGG weights that are not available offline and is left out; Trainer(ssim_loss_weight=...)
+adds a D-SSIM term `1 - SSIM` in its place, losses.py / csrc/loss.hip), backward through the
 renderer to the packed refined record, then the hand-written refiner backward.  Every `accumulate_step`
 micro-steps: gradient all-reduce (DDP average, one flat bucket over RCCL), clip_grad_norm_(2.0) and
 Adam(lr 3e-5, eps 1e-15) on the trainable parameters (by default attn.qkv, utils/optimizers.py:48-52,
@@ -20,6 +21,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from . import losses
 from . import ptv3_ops as ops
 from . import ptv3_train as pt
 from . import train_ops as tops
@@ -185,8 +187,17 @@ class Trainer:
 
     def __init__(self, model: FeaturePredictor, lr=3e-5, eps: float = 1e-15, betas=(0.9, 0.999),
                  grad_clip_norm: float = 2.0, accumulate_step: int = 1, group=None, generator=None,
-                 precision: Optional[str] = None, render: Optional[str] = None, finetune_list=("attn.qkv",)):
-        """precision: "fp32" (default; fp32-accurate refiner forward + backward) or "amp", the reference's
+                 precision: Optional[str] = None, render: Optional[str] = None, finetune_list=("attn.qkv",),
+                 image_l1_loss_weight: float = 1.0, ssim_loss_weight: float = 0.0):
+        """image_l1_loss_weight, ssim_loss_weight: the per-view loss is
+        `image_l1_loss_weight * mean|p - g| + ssim_loss_weight * (1 - SSIM(p, g))`, summed over the views and divided
+        by num_images, len(scenes) and accumulate_step (the normalisation the reference gives image_l1 and its LPIPS
+        term, train.py:277-286).  The L1 weight is the reference's (train.py:206, default 1); the D-SSIM term
+        (the reference's own SSIM, utils/metrics.py:93-135) stands in for the LPIPS term and is off by default.  With
+        ssim_loss_weight == 0 the loss is the torch image_l1; above 0 one losses.image_loss_and_grad call per
+        scene computes loss and derivative, and `last_metrics` holds the batch's image_l1, ssim and train_psnr
+        (train.py:278, :283) as device tensors.
+        precision: "fp32" (default; fp32-accurate refiner forward + backward) or "amp", the reference's
         `training.enable_amp` (train.py:214-299, configs/train/default.gin:11): refiner forward and backward in
         the autocast precision class (ptv3_ops.precision); the renderer, loss and optimiser stay fp32 as in the
         reference (its rasterisation runs outside the autocast region).  No loss scale: the GEMMs scale every
@@ -204,6 +215,12 @@ class Trainer:
         self.precision = precision or os.environ.get("SFX_TRAIN_PREC", "fp32")
         if self.precision not in ops.PRECISIONS:
             raise ValueError(f"precision {self.precision!r}: expected one of {sorted(ops.PRECISIONS)}")
+        if not (image_l1_loss_weight >= 0.0 and ssim_loss_weight >= 0.0):
+            raise ValueError(f"loss weights must be >= 0, got image_l1_loss_weight {image_l1_loss_weight}, "
+                             f"ssim_loss_weight {ssim_loss_weight}")
+        self.image_l1_loss_weight = float(image_l1_loss_weight)
+        self.ssim_loss_weight = float(ssim_loss_weight)
+        self.last_metrics: Optional[Dict[str, Tensor]] = None  # filled by micro_step when ssim_loss_weight > 0
         if isinstance(finetune_list, str):
             finetune_list = (finetune_list,)
         self.finetune_list = tuple(finetune_list or ())
@@ -240,6 +257,9 @@ class Trainer:
         masks = masks or self.masks
         total = 0.0
         num_images = sum(len(im) for im in images)  # counted over the whole batch (train.py:273-281)
+        fused = self.ssim_loss_weight > 0.0  # L1 + D-SSIM and its derivative from one kernel call per scene
+        norm = 1.0 / num_images / len(scenes) / self.accumulate_step
+        sums = None
         for gs, cams, imgs in zip(scenes, cameras, images):
             with ops.precision(self.precision):
                 packed, tape = refine_train(self.model, gs, masks, perms=perms, group=self.group)
@@ -254,13 +274,31 @@ class Trainer:
                     preds, _ = rasterize_packed_to_multiimgs_batched(leaf, self.model.columns(), cams, extra=extra)
                 else:
                     preds, _ = rasterize_gaussians_to_multiimgs(out_gs, cams)
-                loss = image_l1(preds, imgs) / num_images / len(scenes) / self.accumulate_step
-                loss.backward()
+                if fused:
+                    stacked = torch.stack(list(preds), 0)
+                    terms, d_pred = losses.image_loss_and_grad(
+                        stacked, imgs, self.image_l1_loss_weight, self.ssim_loss_weight,
+                        torch.full((len(preds),), norm, device=stacked.device, dtype=torch.float32))
+                    torch.autograd.backward(stacked, d_pred)
+                    loss = terms[:, 3].sum() * norm
+                    # sums over the views of mean|p-g|, SSIM and the unquantised PSNR 20 log10(1 / sqrt(mse))
+                    m = torch.stack([terms[:, 0].sum(), terms[:, 1].sum(), (-10.0 * torch.log10(terms[:, 2])).sum()])
+                    sums = m if sums is None else sums + m
+                    del stacked, d_pred
+                else:
+                    loss = image_l1(preds, imgs)
+                    if self.image_l1_loss_weight != 1.0:  # (the default adds no launch)
+                        loss = loss * self.image_l1_loss_weight
+                    loss = loss / num_images / len(scenes) / self.accumulate_step
+                    loss.backward()
             with ops.precision(self.precision):
                 refine_backward(self.model, tape, leaf.grad)
             total = total + loss.detach()  # summed on the device: one host read per micro-step, not per scene
             del tape, packed, leaf, out_gs, preds
         self.micro += 1
+        if fused:  # averaged as train.py:283 averages train_psnr; device tensors, no host read
+            avg = sums / num_images / len(scenes)
+            self.last_metrics = {"image_l1": avg[0], "ssim": avg[1], "train_psnr": avg[2]}
         loss = float(total)  # (drains the stream)
         _lib.check_lookback("Trainer.micro_step")  # the step's scans / radix passes (pooling, intersection sort)
         return loss
