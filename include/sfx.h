@@ -432,6 +432,9 @@ int sfx_segment_mean(int m, int D, const int* idx_ptr, const int* sorted_idx, co
 /* spconv SubMConv3d indice pairs (indice_key=stage{s}): nbr[n][27], k = (dx+1)*9+(dy+1)*3+(dz+1), -1 absent,
  * duplicate voxels resolve to the lowest point index; mask[n] (optional) = bit k set iff nbr[.][k] >= 0,
  * mask_keys[n] (optional) the same mask widened to the u64 sort-key layout.
+ * Admitted domain: grid_coord in [0, 65535] per axis (serialization depth <= 16), batch in [0, 65534] (NULL: all 0);
+ * the map is exact on all of it.  A neighbour coordinate outside [0, 65535] is absent (-1), never a wrapped match
+ * in another row, column or batch.  Inputs outside the domain are not detected.
  * table_*: 2^log2cap scratch slots.  sfx_subm_permute reorders nbr/mask rows by a permutation (the
  * mask-sorted row order that keeps each GEMM tile's segment union small). */
 int sfx_subm_table_log2(int n);

@@ -20,6 +20,10 @@ Contents (each function cites the reference file:line it restates):
                     render operators (fp64 autograd pins gsplat_ref's hand-written
                     backward restatements) and the seeded edge cases both test
                     files of the render backward share.
+  * geometry_cases -- a brute-force (dict of tuples) SubM neighbour map that
+                    shares no key packing with ptv3_ref or the kernel, pair-list
+                    and pooling references, and the range / batch / table edge
+                    cases the integer geometry is tested on.
 
 Parity status: the glue (gs_utils.py, feature_predictor.py) is pinned by
 golden vectors captured from the reference itself (tests/golden/).  The

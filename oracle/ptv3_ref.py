@@ -104,17 +104,19 @@ def gelu(x):
 
 
 def subm_neighbors(grid: torch.Tensor, batch: torch.Tensor) -> torch.Tensor:
-    """27-neighbour map (k = (dx+1)*9 + (dy+1)*3 + (dz+1)); duplicates resolve to the lowest index."""
+    """27-neighbour map (k = (dx+1)*9 + (dy+1)*3 + (dz+1)); duplicates resolve to the lowest index.
+    Coordinates in [0, 65535] (16-bit key fields), batch < 32768; a neighbour outside that range is absent."""
     g = grid.numpy().astype(np.int64)
     b = batch.numpy().astype(np.int64)
-    pack = lambda bb, x, y, z: (bb << 48) | ((x + 1) << 32) | ((y + 1) << 16) | (z + 1)
+    # the coordinates themselves in 16-bit fields: x + 1 carried into the next field at 65535
+    pack = lambda bb, x, y, z: (bb << 48) | (x << 32) | (y << 16) | z
     keys = pack(b, g[:, 0], g[:, 1], g[:, 2])
     uniq, first = np.unique(keys, return_index=True)  # first occurrence == lowest index
     nbr = np.full((g.shape[0], 27), -1, dtype=np.int64)
     for k in range(27):
         dx, dy, dz = k // 9 - 1, (k // 3) % 3 - 1, k % 3 - 1
         x, y, z = g[:, 0] + dx, g[:, 1] + dy, g[:, 2] + dz
-        ok = (x >= 0) & (y >= 0) & (z >= 0)
+        ok = (x >= 0) & (y >= 0) & (z >= 0) & (x <= 65535) & (y <= 65535) & (z <= 65535)
         q = pack(b, x, y, z)
         pos = np.clip(np.searchsorted(uniq, q), 0, len(uniq) - 1)
         hit = ok & (uniq[pos] == q)

@@ -3,7 +3,7 @@
 // Pointcept Block.cpe).
 //
 // An open-addressing hash (linear probing, 2^k slots >= 2n) maps the packed
-// voxel key (batch, x+1, y+1, z+1) -> lowest point index owning that voxel
+// voxel key (batch, x, y, z) -> lowest point index owning that voxel
 // (atomicMin: a deterministic rule for duplicate voxels, where spconv's GPU
 // hash picks an arbitrary duplicate).  The query writes nbr[i][k] for the 27
 // offsets k = (dx+1)*9 + (dy+1)*3 + (dz+1) (spconv weight layout
@@ -17,9 +17,15 @@ namespace {
 
 constexpr unsigned long long EMPTY = ~0ull;
 
+// Admitted domain: x, y, z in [0, kCoordMax] (16-bit fields, depth <= 16), batch in [0, 65534].  The coordinates are
+// packed as they are: the query rejects a neighbour outside [0, kCoordMax] before packing, so no field can carry
+// into the next one (the earlier x + 1 form did at 65535: 65536 ran into the field above and matched a voxel of
+// another row, column or batch).  The all-ones EMPTY marker needs batch = 65535, which is outside the domain.
+constexpr int kCoordMax = 65535;
+
 __device__ __forceinline__ unsigned long long pack(int b, int x, int y, int z) {
-  return ((unsigned long long)(unsigned)b << 48) | ((unsigned long long)(unsigned)(x + 1) << 32) |
-         ((unsigned long long)(unsigned)(y + 1) << 16) | (unsigned long long)(unsigned)(z + 1);
+  return ((unsigned long long)(unsigned)b << 48) | ((unsigned long long)(unsigned)x << 32) |
+         ((unsigned long long)(unsigned)y << 16) | (unsigned long long)(unsigned)z;
 }
 
 __device__ __forceinline__ unsigned slot_of(unsigned long long key, int log2cap) {
@@ -70,7 +76,7 @@ __global__ void subm_query_kernel(int n, const int* __restrict__ grid, const int
   const int x = grid[3 * i] + k / 9 - 1, y = grid[3 * i + 1] + (k / 3) % 3 - 1, z = grid[3 * i + 2] + k % 3 - 1;
   const unsigned cmask = (1u << log2cap) - 1u;
   int out = -1;
-  if (x >= 0 && y >= 0 && z >= 0) {
+  if (x >= 0 && y >= 0 && z >= 0 && x <= kCoordMax && y <= kCoordMax && z <= kCoordMax) {
     const unsigned long long key = pack(batch ? batch[i] : 0, x, y, z);
     unsigned s = slot_of(key, log2cap);
     while (true) {
@@ -303,7 +309,8 @@ int sfx_subm_pair_lists(int n, const int* nbr, void* ws, size_t ws_bytes, int* p
 // pair_off (device, 28 ints) as written by sfx_subm_pairs, num_pairs = pair_off[27]
 int sfx_subm_pair_pos(int n, long long num_pairs, const int* pair_out, const int* pair_off, int* pair_pos,
                       void* stream) {
-  SFX_REQUIRE(n >= 0 && num_pairs >= 0 && num_pairs <= 26ll * n, "sfx_subm_pair_pos: bad sizes");
+  // (27 n: lists built with the centre offset hold up to that many pairs)
+  SFX_REQUIRE(n >= 0 && num_pairs >= 0 && num_pairs <= 27ll * n, "sfx_subm_pair_pos: bad sizes");
   if (n == 0) return SFX_OK;
   SFX_REQUIRE(pair_pos && (num_pairs == 0 || (pair_out && pair_off)), "sfx_subm_pair_pos: null buffer");
   hipStream_t st = sfx::as_stream(stream);

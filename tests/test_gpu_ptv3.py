@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ptv3_ref, serialize_ref
+from oracle import geometry_cases, ptv3_ref, serialize_ref
 from splatformer_amd import ptv3_ops as ops
 from splatformer_amd.feature_predictor import FeaturePredictor
 from splatformer_amd.scenes import make_scene, to_device
@@ -508,18 +508,9 @@ def test_pooling_geometry_exact(device, stride, B, perm, res):
 
     # the reference's integer math on the oracle's serialization, rows in logical (permuted) order
     c_ref, _, _, _ = serialize_ref.serialization(grid.numpy(), batch.numpy(), ptv3_ref.ORDERS, None)
-    code = torch.from_numpy(c_ref)[perm]
-    pd = (stride - 1).bit_length()
-    if pd > depth:
-        pd = 0
-    code = code >> 3 * pd
-    _, cluster, counts = torch.unique(code[0], sorted=True, return_inverse=True, return_counts=True)
-    indices = torch.sort(cluster, stable=True).indices
-    ptr_ref = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)])
-    head = indices[ptr_ref[:-1]]
-    code_h = code[:, head]
-    order_ref = torch.argsort(code_h, stable=True)
-    inv_ref = torch.zeros_like(order_ref).scatter_(1, order_ref, torch.arange(code_h.shape[1]).repeat(4, 1))
+    r = geometry_cases.pooling_ref(torch.from_numpy(c_ref)[perm], stride, depth)
+    pd, cluster, counts, indices, ptr_ref = r["pd"], r["cluster"], r["counts"], r["indices"], r["ptr"]
+    head, code_h, order_ref, inv_ref = r["head"], r["code_h"], r["order"], r["inverse"]
 
     assert m == len(counts)
     assert torch.equal(new.pooling_inverse.cpu().long(), cluster)
