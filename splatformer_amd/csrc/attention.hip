@@ -22,9 +22,7 @@
 // the B operand (no LDS round trip for P).
 #include <cstdlib>
 
-#include <type_traits>
-
-#include "common.h"
+#include "attn_common.h"
 
 #ifndef SFX_ATTN_OCC16
 #define SFX_ATTN_OCC16 4  // workgroups per CU the d = 16 split kernel is compiled for
@@ -32,16 +30,77 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
+using namespace sfxa;
 
-constexpr int KMAX = 128;
+// ---- exact fp32 kernels (SFX_ATTN_PREC=fp32): shared steps -------------------------------------------------
+// LDS rows of KMAX keys / queries: Q and K at stride DP, V at stride DPV, zero beyond D where a lane-indexed column
+// read (dd = lane) needs no mask.
 
-// V^T chunk swizzle: the 16-byte chunk c (8 keys) of V^T row dd sits at chunk c ^ vt_swz(dd), 2 x the parity of
-// dd's 4-row group.  The staging's transposed dword stores (rows 4 ch .. 4 ch + 3 of 4-8 column chunks per 32
-// lanes) were 2- / 3- / 4-way bank conflicts at d = 16 / 24 / 32 (the stride-136 rows put every other chunk group on
-// one bank set); swizzled they are 1- / 2- / 2-way (free for ds_write_b32), and the fragment reads stay conflict-
-// free (tools/attn_banks.py)
-__device__ __forceinline__ int vt_swz(int dd) { return (__builtin_popcount((unsigned)(dd >> 2)) & 1) << 1; }
+// zero the V padding columns D..31 once
+template <int D, int DPV>
+__device__ __forceinline__ void exact_zero_vpad(float* Vs, int tid) {
+  if (D < 32)
+    for (int e = tid; e < KMAX * (32 - D) / 4; e += 256) {
+      const int row = e / ((32 - D) / 4), c4 = e - row * ((32 - D) / 4);
+      *reinterpret_cast<float4*>(&Vs[row * DPV + D + 4 * c4]) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+// gather matrices M0 .. M0 + NM - 1 of (q, k, v) of this head through rows[] (zero rows where rows[] < 0):
+// KMAX rows x NM mats x D/4 float4; q is scaled on the way in
+template <int D, int M0, int NM, int DP, int DPV>
+__device__ __forceinline__ void exact_gather(const float* __restrict__ qkv, const int* rows, long long ld, int C,
+                                             int head, float scale, float* Qs, float* Ks, float* Vs, int tid) {
+  constexpr int CH = D / 4;
+  for (int e = tid; e < KMAX * NM * CH; e += 256) {
+    const int row = e / (NM * CH);
+    const int rem = e - row * NM * CH;
+    const int m = NM == 1 ? 0 : rem / CH, ch = rem - m * CH;  // matrix M0 + m
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int src = rows[row];
+    if (src >= 0) v = *reinterpret_cast<const float4*>(qkv + (long long)src * ld + (M0 + m) * C + head * D + 4 * ch);
+    if (M0 == 0 && m == 0) {
+      v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
+      *reinterpret_cast<float4*>(&Qs[row * DP + 4 * ch]) = v;
+    } else if (M0 + m == 1) {
+      *reinterpret_cast<float4*>(&Ks[row * DP + 4 * ch]) = v;
+    } else {
+      *reinterpret_cast<float4*>(&Vs[row * DPV + 4 * ch]) = v;
+    }
+  }
+}
+// c += a b^T on v_mfma_f32_32x32x2_f32, four k-values of this lane half
+__device__ __forceinline__ floatx16 exact_mfma4(float4 a, float4 b, floatx16 c) {
+  c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, c, 0, 0, 0);
+}
+// this lane's half (HALF = D / 2 k-values per lane half in S = K Q^T) of LDS row `row`
+template <int HALF>
+__device__ __forceinline__ void exact_load_half(const float* row, int h, float4 (&v)[HALF / 4]) {
+#pragma unroll
+  for (int c = 0; c < HALF / 4; ++c) v[c] = *reinterpret_cast<const float4*>(row + h * HALF + 4 * c);
+}
+// S^T[key][query] for this wave's 32 queries, 4 key blocks of 32; qv: this lane's (scaled) query half
+template <int HALF, int DP>
+__device__ __forceinline__ void exact_scores(const float* Ks, const float4 (&qv)[HALF / 4], int l32, int h,
+                                             floatx16 (&s)[4]) {
+  score_zero(s);
+#pragma unroll
+  for (int c = 0; c < HALF / 4; ++c)
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+      s[kb] = exact_mfma4(*reinterpret_cast<const float4*>(&Ks[(kb * 32 + l32) * DP + h * HALF + 4 * c]), qv[c], s[kb]);
+}
+// o^T[dd][query] += sum_key M[key][dd] b^T[key][query] for key block kb, b from registers; mcol = &M[4 h][l32]
+// (the + 4 h of the key is folded into it)
+template <int DPV>
+__device__ __forceinline__ floatx16 exact_col_mfma(const float* mcol, int kb, const floatx16& b, floatx16 o) {
+#pragma unroll
+  for (int st = 0; st < 16; ++st)
+    o = __builtin_amdgcn_mfma_f32_32x32x2f32(mcol[score_key(kb, st, 0) * DPV], b[st], o, 0, 0, 0);
+  return o;
+}
 
 template <int D>
 __global__ void __launch_bounds__(256, 2)
@@ -50,7 +109,6 @@ window_attn_kernel(const float* __restrict__ qkv, const int* __restrict__ order,
   constexpr int DP = D + 4;   // Q/K rows: conflict-free ds_read_b128 for D = 16, 24, 32
   constexpr int DPV = 40;     // V rows padded to 32 (+8): the P.V MFMA reads V^T[dd = lane][key] with no
                               // masking for dd >= D, and the two half-waves (keys 4 apart) hit disjoint banks
-  constexpr int HALF = D / 2;  // k-values per lane half in S = K Q^T
   __shared__ __attribute__((aligned(16))) float Qs[KMAX * DP];
   __shared__ __attribute__((aligned(16))) float Ks[KMAX * DP];
   __shared__ __attribute__((aligned(16))) float Vs[KMAX * DPV];
@@ -62,78 +120,20 @@ window_attn_kernel(const float* __restrict__ qkv, const int* __restrict__ order,
   const long long ld = 3ll * C;
 
   if (tid < KMAX) rows[tid] = tid < Kwin ? order[key_start + tid] : -1;
-  if (D < 32)  // zero the V padding columns D..31 once
-    for (int e = tid; e < KMAX * (32 - D) / 4; e += 256) {
-      const int row = e / ((32 - D) / 4), c4 = e - row * ((32 - D) / 4);
-      *reinterpret_cast<float4*>(&Vs[row * DPV + D + 4 * c4]) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+  exact_zero_vpad<D, DPV>(Vs, tid);
   __syncthreads();
-  // gather q/k/v rows of this head: KMAX rows x 3 mats x D/4 float4
-  constexpr int CH = D / 4;
-  for (int e = tid; e < KMAX * 3 * CH; e += 256) {
-    const int row = e / (3 * CH);
-    const int rem = e - row * 3 * CH;
-    const int mat = rem / CH, ch = rem - mat * CH;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int src = rows[row];
-    if (src >= 0) v = *reinterpret_cast<const float4*>(qkv + (long long)src * ld + mat * C + head * D + 4 * ch);
-    if (mat == 0) {
-      v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
-      *reinterpret_cast<float4*>(&Qs[row * DP + 4 * ch]) = v;
-    } else if (mat == 1) {
-      *reinterpret_cast<float4*>(&Ks[row * DP + 4 * ch]) = v;
-    } else {
-      *reinterpret_cast<float4*>(&Vs[row * DPV + 4 * ch]) = v;
-    }
-  }
+  exact_gather<D, 0, 3, DP, DPV>(qkv, rows, ld, C, head, scale, Qs, Ks, Vs, tid);
   __syncthreads();
 
-  // S^T[key][query] for this wave's 32 queries, 4 key blocks of 32
+  constexpr int HALF = D / 2;
+  float4 qv[HALF / 4];
+  exact_load_half<HALF>(&Qs[(32 * wid + l32) * DP], h, qv);
   floatx16 s[4];
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
-  const float* qrow = &Qs[(32 * wid + l32) * DP + h * HALF];
-#pragma unroll
-  for (int c = 0; c < HALF / 4; ++c) {
-    const float4 qv = *reinterpret_cast<const float4*>(qrow + 4 * c);
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-      const float4 kv = *reinterpret_cast<const float4*>(&Ks[(kb * 32 + l32) * DP + h * HALF + 4 * c]);
-      s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.x, qv.x, s[kb], 0, 0, 0);
-      s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.y, qv.y, s[kb], 0, 0, 0);
-      s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.z, qv.z, s[kb], 0, 0, 0);
-      s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.w, qv.w, s[kb], 0, 0, 0);
-    }
-  }
-  // softmax over keys (register axis + the other half-wave); keys >= Kwin only exist in short windows
-  if (Kwin < KMAX) {
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (key >= Kwin) s[kb][r] = -INFINITY;
-      }
-  }
-  float mx = -INFINITY;
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float e = __expf(s[kb][r] - mx);
-      s[kb][r] = e;
-      sum += e;
-    }
-  sum += __shfl_xor(sum, 32, 64);
-  const float rinv = 1.f / sum;
+  exact_scores<HALF, DP>(Ks, qv, l32, h, s);
+  // softmax over keys; keys >= Kwin only exist in short windows
+  if (Kwin < KMAX) score_mask(s, h, Kwin);
+  const float mx = score_max(s);
+  const float rinv = 1.f / score_exp<false>(s, mx);
 #pragma unroll
   for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
@@ -145,27 +145,14 @@ window_attn_kernel(const float* __restrict__ qkv, const int* __restrict__ order,
   for (int r = 0; r < 16; ++r) o[r] = 0.f;
   const float* vcol = &Vs[4 * h * DPV + l32];
 #pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int st = 0; st < 16; ++st) {
-      const int key0 = kb * 32 + (st & 3) + 8 * (st >> 2);  // + 4h folded into vcol
-      o = __builtin_amdgcn_mfma_f32_32x32x2f32(vcol[key0 * DPV], s[kb][st], o, 0, 0, 0);
-    }
+  for (int kb = 0; kb < 4; ++kb) o = exact_col_mfma<DPV>(vcol, kb, s[kb], o);
 
-  // scatter: query 32*wid + l32 (lane column), dd rows (r&3) + 8(r>>2) + 4h
+  // scatter: query 32*wid + l32 (lane column)
   const int qi = 32 * wid + l32;
   const int qpos = key_start + qi;
-  if (qi < Kwin && qpos >= query_start) {
-    float* dst = out + (long long)rows[qi] * C + head * D;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int dd = 8 * g + 4 * h;
-      if (dd + 3 < D) {
-        *reinterpret_cast<float4*>(dst + dd) = make_float4(o[4 * g + 0], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]);
-      }
-    }
-  }
+  if (qi < Kwin && qpos >= query_start) store_ot<D>(out + (long long)rows[qi] * C + head * D, o, h);
 }
+
 
 // ---- flash mode: windows of up to 2^20 keys, per-window key count -------------------------------------
 // Reference pointtransformer_v3.py:121-123 (patch 1024 when enable_flash) and Pointcept's SerializedAttention
@@ -186,7 +173,6 @@ window_attn_flash_kernel(const float* __restrict__ qkv, const int* __restrict__ 
   constexpr int DP = D + 4;
   constexpr int DPV = 40;
   constexpr int HALF = D / 2;
-  constexpr int CH = D / 4;
   __shared__ __attribute__((aligned(16))) float Qs[KMAX * DP];
   __shared__ __attribute__((aligned(16))) float Ks[KMAX * DP];
   __shared__ __attribute__((aligned(16))) float Vs[KMAX * DPV];
@@ -201,25 +187,12 @@ window_attn_flash_kernel(const float* __restrict__ qkv, const int* __restrict__ 
   const long long ld = 3ll * C;
 
   if (tid < KMAX) qrows[tid] = q0 + tid < count ? order[key_start + q0 + tid] : -1;
-  if (D < 32)
-    for (int e = tid; e < KMAX * (32 - D) / 4; e += 256) {
-      const int row = e / ((32 - D) / 4), c4 = e - row * ((32 - D) / 4);
-      *reinterpret_cast<float4*>(&Vs[row * DPV + D + 4 * c4]) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+  exact_zero_vpad<D, DPV>(Vs, tid);
   __syncthreads();
-  for (int e = tid; e < KMAX * CH; e += 256) {
-    const int row = e / CH, ch = e - row * CH;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int src = qrows[row];
-    if (src >= 0) v = *reinterpret_cast<const float4*>(qkv + (long long)src * ld + head * D + 4 * ch);
-    v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
-    *reinterpret_cast<float4*>(&Qs[row * DP + 4 * ch]) = v;
-  }
+  exact_gather<D, 0, 1, DP, DPV>(qkv, qrows, ld, C, head, scale, Qs, Ks, Vs, tid);
   __syncthreads();
   float4 qv[HALF / 4];
-#pragma unroll
-  for (int c = 0; c < HALF / 4; ++c)
-    qv[c] = *reinterpret_cast<const float4*>(&Qs[(32 * wid + l32) * DP + h * HALF + 4 * c]);
+  exact_load_half<HALF>(&Qs[(32 * wid + l32) * DP], h, qv);
 
   float m_run = -INFINITY, l_run = 0.f;
   floatx16 o;
@@ -232,87 +205,30 @@ window_attn_flash_kernel(const float* __restrict__ qkv, const int* __restrict__ 
     __syncthreads();  // the previous block's K/V fragment reads are done
     if (tid < KMAX) krows[tid] = tid < nk ? order[key_start + k0 + tid] : -1;
     __syncthreads();
-    for (int e = tid; e < KMAX * 2 * CH; e += 256) {
-      const int row = e / (2 * CH);
-      const int rem = e - row * 2 * CH;
-      const int mat = rem / CH, ch = rem - mat * CH;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      const int src = krows[row];
-      if (src >= 0) v = *reinterpret_cast<const float4*>(qkv + (long long)src * ld + (mat + 1) * C + head * D + 4 * ch);
-      if (mat == 0) *reinterpret_cast<float4*>(&Ks[row * DP + 4 * ch]) = v;
-      else *reinterpret_cast<float4*>(&Vs[row * DPV + 4 * ch]) = v;
-    }
+    exact_gather<D, 1, 2, DP, DPV>(qkv, krows, ld, C, head, scale, Qs, Ks, Vs, tid);
     __syncthreads();
 
     floatx16 s[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
-#pragma unroll
-    for (int c = 0; c < HALF / 4; ++c) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        const float4 kv = *reinterpret_cast<const float4*>(&Ks[(kb * 32 + l32) * DP + h * HALF + 4 * c]);
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.x, qv[c].x, s[kb], 0, 0, 0);
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.y, qv[c].y, s[kb], 0, 0, 0);
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.z, qv[c].z, s[kb], 0, 0, 0);
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.w, qv[c].w, s[kb], 0, 0, 0);
-      }
-    }
-    if (nk < KMAX) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          if (key >= nk) s[kb][r] = -INFINITY;
-        }
-    }
-    float bm = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) bm = fmaxf(bm, s[kb][r]);
-    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-    const float m_new = fmaxf(m_run, bm);  // finite: every block holds at least one key
+    exact_scores<HALF, DP>(Ks, qv, l32, h, s);
+    if (nk < KMAX) score_mask(s, h, nk);
+    const float m_new = fmaxf(m_run, score_max(s));  // finite: every block holds at least one key
     const float corr = __expf(m_run - m_new);
-    float sum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = __expf(s[kb][r] - m_new);
-        s[kb][r] = e;
-        sum += e;
-      }
-    sum += __shfl_xor(sum, 32, 64);
-    l_run = l_run * corr + sum;
+    l_run = l_run * corr + score_exp<false>(s, m_new);
     m_run = m_new;
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[r] *= corr;
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int st = 0; st < 16; ++st) {
-        const int key0 = kb * 32 + (st & 3) + 8 * (st >> 2);
-        o = __builtin_amdgcn_mfma_f32_32x32x2f32(vcol[key0 * DPV], s[kb][st], o, 0, 0, 0);
-      }
+    for (int kb = 0; kb < 4; ++kb) o = exact_col_mfma<DPV>(vcol, kb, s[kb], o);
   }
 
   const float rinv = 1.f / l_run;
-  const int qi = q0 + 32 * wid + l32;
-  if (qi < count && key_start + qi >= query_start) {
-    float* dst = out + (long long)qrows[32 * wid + l32] * C + head * D;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int dd = 8 * g + 4 * h;
-      if (dd + 3 < D)
-        *reinterpret_cast<float4*>(dst + dd) = make_float4(o[4 * g + 0] * rinv, o[4 * g + 1] * rinv,
-                                                           o[4 * g + 2] * rinv, o[4 * g + 3] * rinv);
-    }
-  }
+  for (int r = 0; r < 16; ++r) o[r] *= rinv;
+  const int qi = q0 + 32 * wid + l32;
+  if (qi < count && key_start + qi >= query_start)
+    store_ot<D>(out + (long long)qrows[32 * wid + l32] * C + head * D, o, h);
 }
+
 
 // ---- flash mode backward (training with enable_flash=True) ----------------------------------------------
 // Two launches, fp32 VALU (each lane owns one query or one key; the block's other rows stream through LDS as
@@ -499,102 +415,34 @@ flash_bwd_key_kernel(const float* __restrict__ qkv, const int* __restrict__ orde
 // in registers.  Same fp32-level accuracy, half the MFMAs and two-thirds of the LDS images.
 // ONE (sfx_set_precision(1), the reference's autocast class): F16 the leading product h*h only, bf16x3 the three
 // leading term products (16-bit significands)
-template <int D, bool F16, bool ONE = false>
-__global__ void __launch_bounds__(256, D == 16 ? SFX_ATTN_OCC16 : 3)
-window_attn_split_kernel(const float* __restrict__ qkv, const int* __restrict__ order, const int* __restrict__ win,
-                         int Kwin, int C, float scale, float* __restrict__ out,
-                         const unsigned long long* __restrict__ qkv_amax, unsigned qkv_tag, int nwin) {
-  typedef typename std::conditional<F16, _Float16, __bf16>::type elem_t;
-  typedef elem_t bf16x8 __attribute__((ext_vector_type(8)));  // (fragment type: bf16 or fp16 terms)
-  constexpr int NT = F16 ? 2 : 3;            // terms per operand
-  constexpr int KD = D == 16 ? 16 : 32;
-  constexpr int NKS = KD / 16;
-  constexpr int QROW = KD == 16 ? 48 : 64;  // bytes per Q/K term row
-  constexpr int VST = 136;                  // V^T row stride (16-bit elements)
-  constexpr int QK_BYTES = NT * KMAX * QROW;
-  constexpr int V_BYTES = NT * D * VST * 2;
-  // operand scales (F16): qkv by sq, probabilities by 2^14
-  float sq = 1.f, iq = 1.f;
-  if constexpr (F16) {
-    const float m = sfx::read_amax(qkv_amax, qkv_tag);
-    int e = 0;
-    if (m > 0.f && m <= 3.4028235e38f) {
-      (void)frexpf(m, &e);
-      e = 15 - e;
-      e = e > 126 ? 126 : (e < -126 ? -126 : e);
-    }
-    sq = ldexpf(1.f, e);
-    iq = ldexpf(1.f, -e);
+//
+// The steps window_attn_split_kernel and window_attn_split_flash_kernel share (256 threads; rows[]: the points of
+// the 128 keys, -1 past the count); layouts, fragments and term products are attn_common.h's.
+
+// this lane's query slices (B operand of S^T = K Q^T): dd = 16 ks + 8h + j, zero past D; scale * log2(e) folded in
+template <int D, bool F16, int NKS>
+__device__ __forceinline__ void fwd_query_frags(const float* __restrict__ qkv, int src, long long ld, int head, int h,
+                                                float scale, float sq, frag_t<F16> (&qf)[NKS][nterms(F16)]) {
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) {
+    float4 a, b;
+    load8<D>(qkv + (long long)(src < 0 ? 0 : src) * ld + head * D, 16 * ks + 8 * h, src >= 0, a, b);
+    q_frag<F16>(a, b, scale * 1.4426950408889634f, sq, qf[ks]);
   }
-  auto split = [&](float4 v, float sc, uint2 (&t)[NT]) {
-    if constexpr (F16) sfx::split2h(v, sc, t); else sfx::split3(v, t);
-  };
-  __shared__ __attribute__((aligned(16))) char lds[QK_BYTES + V_BYTES];
-  __shared__ int rows[KMAX];
-  char* Ks = lds;
-  unsigned short* Vt = reinterpret_cast<unsigned short*>(lds + QK_BYTES);
-  // byte offset of 16-byte chunk c of term row r
-  auto qk_off = [](int r, int c) -> int {
-    return KD == 16 ? r * 48 + c * 16 : r * 64 + (((c ^ (r >> 2)) & 3) << 4);
-  };
-
-  // XCD-aware numbering over a 1-D grid padded to a multiple of 8: consecutive blocks go round-robin to the 8
-  // XCDs, so logical id L = xcd * (grid / 8) + slot puts all heads of a window on one XCD back to back -- the
-  // 128-byte qkv lines its heads share (d = 16: two heads per line) are fetched from HBM once into that L2.
-  const int heads = C / D;
-  const int nb = (int)gridDim.x;
-  const int L = (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8);
-  if (L >= nwin * heads) return;
-  const int w = L / heads, head = L - w * heads;
-  const int key_start = win[2 * w], query_start = win[2 * w + 1];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, h = lane >> 5, l32 = lane & 31;
-  const long long ld = 3ll * C;
-
-  if (tid < KMAX) rows[tid] = tid < Kwin ? order[key_start + tid] : -1;
-  // zero padding: K columns D..KD-1 (never written by the staging below)
-  if (D < KD)
-    for (int rr = tid; rr < NT * KMAX; rr += 256)  // term rows, term-major
-      *reinterpret_cast<uint4*>(Ks + qk_off(rr, D / 8)) = make_uint4(0, 0, 0, 0);
-  __syncthreads();
-  // gather + split, one matrix at a time (wave-uniform paths): q, k rows as KMAX x D/4 float4; v as
-  // key pairs x D/4 float4 so the transposed V^T writes are whole dwords (keys 2m, 2m+1 are adjacent
-  // in the permuted order)
+}
+// gather + split, one matrix at a time (wave-uniform paths): k rows as KMAX x D/4 float4 into the K term image; v as
+// key pairs x D/4 float4 so the transposed V^T writes are whole dwords (keys 2m, 2m+1 are adjacent in the permuted
+// order)
+template <int D, int KD, bool F16>
+__device__ __forceinline__ void fwd_stage_kv(const float* __restrict__ qkv, const int* rows, long long ld, int C,
+                                             int head, float sq, char* Ks, unsigned short* Vt, int tid) {
   constexpr int CH = D / 4;
-  typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-  // this lane's query slices (B operand of S^T = K Q^T): dd = 16 ks + 8h + j, zero past D
-  bf16x8 qf[NKS][NT];
-  {
-    const int src = rows[32 * wid + l32];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const int d0 = 16 * ks + 8 * h;
-      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-      if (src >= 0 && d0 < D) {
-        const float* qp = qkv + (long long)src * ld + head * D + d0;
-        a = *reinterpret_cast<const float4*>(qp);
-        if (d0 + 4 < D) b = *reinterpret_cast<const float4*>(qp + 4);
-      }
-      // scale * log2(e) folded into q: the softmax exponentials are plain exp2
-      const float qs = scale * 1.4426950408889634f;
-      a.x *= qs; a.y *= qs; a.z *= qs; a.w *= qs;
-      b.x *= qs; b.y *= qs; b.z *= qs; b.w *= qs;
-      uint2 ta[NT], tb[NT];
-      split(a, sq, ta);  // (|q * qs| <= |q|: the qkv bound holds)
-      split(b, sq, tb);
-#pragma unroll
-      for (int q = 0; q < NT; ++q) qf[ks][q] = __builtin_bit_cast(bf16x8, (uintx4){ta[q].x, ta[q].y, tb[q].x, tb[q].y});
-    }
-  }
   for (int e = tid; e < KMAX * CH; e += 256) {
     const int row = e / CH, ch = e - row * CH;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     const int src = rows[row];
     if (src >= 0) v = *reinterpret_cast<const float4*>(qkv + (long long)src * ld + C + head * D + 4 * ch);
-    uint2 t[NT];
-    split(v, sq, t);
-    const int o = qk_off(row, ch >> 1) + ((ch & 1) << 3);
-#pragma unroll
-    for (int q = 0; q < NT; ++q) *reinterpret_cast<uint2*>(Ks + q * KMAX * QROW + o) = t[q];
+    stage_row<KD, F16>(Ks, row, ch, v, sq);
   }
   for (int e = tid; e < (KMAX / 2) * CH; e += 256) {
     const int kp = e / CH, ch = e - kp * CH;
@@ -603,378 +451,84 @@ window_attn_split_kernel(const float* __restrict__ qkv, const int* __restrict__ 
     float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
     if (s0 >= 0) v0 = *reinterpret_cast<const float4*>(qkv + (long long)s0 * ld + 2 * C + head * D + 4 * ch);
     if (s1 >= 0) v1 = *reinterpret_cast<const float4*>(qkv + (long long)s1 * ld + 2 * C + head * D + 4 * ch);
-    uint2 t0[NT], t1[NT];
-    split(v0, sq, t0);
-    split(v1, sq, t1);
-    const int kk = row & 15;  // even: keys row, row + 1 land on adjacent positions
-    const int pos = (row & ~15) + 8 * ((kk >> 2) & 1) + (((kk >> 3) << 2) | (kk & 3));
-#pragma unroll
-    for (int q = 0; q < NT; ++q) {
-      unsigned* vt = reinterpret_cast<unsigned*>(Vt + (q * D + 4 * ch) * VST + (pos ^ (8 * vt_swz(4 * ch))));
-      vt[0] = (t0[q].x & 0xffffu) | (t1[q].x << 16);
-      vt[VST / 2] = (t0[q].x >> 16) | (t1[q].x & 0xffff0000u);
-      vt[VST] = (t0[q].y & 0xffffu) | (t1[q].y << 16);
-      vt[3 * VST / 2] = (t0[q].y >> 16) | (t1[q].y & 0xffff0000u);
-    }
+    stage_pair<D, F16>(nullptr, Vt, row, ch, v0, v1, sq);
   }
-  __syncthreads();
-
-  // term products, smallest first
-  constexpr int NP = F16 ? 3 : 6;
-  constexpr int QA[6] = {F16 ? 1 : 2, F16 ? 0 : 1, 0, 1, 0, 0}, QB[6] = {0, 1, F16 ? 0 : 2, 0, 1, 0};
-  constexpr int JS = ONE ? (F16 ? 2 : 3) : 0;  // first term product formed
-  auto mfma = [](const bf16x8& a, const bf16x8& b, floatx16 c) -> floatx16 {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  };
-  // S^T[key][query] for this wave's 32 queries, 4 key blocks of 32
-  floatx16 s[4];
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
+}
+// S^T[key][query] for this wave's 32 queries, 4 key blocks of 32, unscaled (F16: S was formed from sq-scaled q and k)
+template <int KD, bool F16, bool ONE, int NKS>
+__device__ __forceinline__ void fwd_scores(const char* Ks, const frag_t<F16> (&qf)[NKS][nterms(F16)], int l32, int h,
+                                           float iq, floatx16 (&s)[4]) {
+  score_zero(s);
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
-      bf16x8 kf[NT];
-#pragma unroll
-      for (int q = 0; q < NT; ++q)
-        kf[q] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(
-                                               Ks + q * KMAX * QROW + qk_off(kb * 32 + l32, 2 * ks + h)));
-#pragma unroll
-      for (int j = JS; j < NP; ++j) s[kb] = mfma(kf[QA[j]], qf[ks][QB[j]], s[kb]);
+      frag_t<F16> kf[nterms(F16)];
+      row_frag<KD, F16>(Ks, kb * 32 + l32, 2 * ks + h, kf);
+      s[kb] = mfma_terms<F16, ONE>(kf, qf[ks], s[kb]);
     }
   }
-  if constexpr (F16) {  // S was formed from sq-scaled q and k
+  if constexpr (F16) {
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[kb][r] = s[kb][r] * iq * iq;
   }
-  // softmax over keys (register axis + the other half-wave); keys >= Kwin only exist in short windows
-  if (Kwin < KMAX) {
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (key >= Kwin) s[kb][r] = -INFINITY;
-      }
-  }
-  float mx = -INFINITY;
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float e = __builtin_amdgcn_exp2f(s[kb][r] - mx);
-      s[kb][r] = e;
-      sum += e;
-    }
-  sum += __shfl_xor(sum, 32, 64);
-  const float rinv = 1.f / sum;
+}
 
-  // O^T[dd][query] = sum_key V^T[dd][key] P^T[key][query]
+template <int D, bool F16, bool ONE = false>
+__global__ void __launch_bounds__(256, D == 16 ? SFX_ATTN_OCC16 : 3)
+window_attn_split_kernel(const float* __restrict__ qkv, const int* __restrict__ order, const int* __restrict__ win,
+                         int Kwin, int C, float scale, float* __restrict__ out,
+                         const unsigned long long* __restrict__ qkv_amax, unsigned qkv_tag, int nwin) {
+  constexpr int NT = nterms(F16);           // terms per operand
+  constexpr int KD = D == 16 ? 16 : 32;
+  constexpr int NKS = KD / 16;
+  constexpr int QK_BYTES = NT * KMAX * row_bytes(KD);
+  constexpr int V_BYTES = NT * D * VST * 2;
+  // operand scales (F16): qkv by sq, probabilities by 2^14
+  float sq = 1.f, iq = 1.f;
+  if constexpr (F16) sq = sfx::pow2_scale(sfx::read_amax(qkv_amax, qkv_tag), iq);
+  __shared__ __attribute__((aligned(16))) char lds[QK_BYTES + V_BYTES];
+  __shared__ int rows[KMAX];
+  char* Ks = lds;
+  unsigned short* Vt = reinterpret_cast<unsigned short*>(lds + QK_BYTES);
+
+  const int heads = C / D;
+  const int L = xcd_logical_id();
+  if (L >= nwin * heads) return;
+  const int w = L / heads, head = L - w * heads;
+  const int key_start = win[2 * w], query_start = win[2 * w + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, h = lane >> 5, l32 = lane & 31;
+  const long long ld = 3ll * C;
+
+  if (tid < KMAX) rows[tid] = tid < Kwin ? order[key_start + tid] : -1;
+  zero_row_pad<D, KD>(Ks, NT * KMAX, tid);
+  __syncthreads();
+  frag_t<F16> qf[NKS][NT];
+  fwd_query_frags<D, F16, NKS>(qkv, rows[32 * wid + l32], ld, head, h, scale, sq, qf);
+  fwd_stage_kv<D, KD, F16>(qkv, rows, ld, C, head, sq, Ks, Vt, tid);
+  __syncthreads();
+
+  floatx16 s[4];
+  fwd_scores<KD, F16, ONE, NKS>(Ks, qf, l32, h, iq, s);
+  // softmax over keys; keys >= Kwin only exist in short windows
+  if (Kwin < KMAX) score_mask(s, h, Kwin);
+  const float mx = score_max(s);
+  const float rinv = 1.f / score_exp<true>(s, mx);
+
   floatx16 o;
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] = 0.f;
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-      uint2 a[NT], b[NT];
-      // unnormalised exp values (0, 1] (F16: scaled by 2^14); 1/sum is applied to O
-      split(make_float4(s[kb][8 * st + 0], s[kb][8 * st + 1], s[kb][8 * st + 2], s[kb][8 * st + 3]), 16384.f, a);
-      split(make_float4(s[kb][8 * st + 4], s[kb][8 * st + 5], s[kb][8 * st + 6], s[kb][8 * st + 7]), 16384.f, b);
-      bf16x8 pf[NT], vf[NT];
-#pragma unroll
-      for (int q = 0; q < NT; ++q) {
-        pf[q] = __builtin_bit_cast(bf16x8, make_uint4(a[q].x, a[q].y, b[q].x, b[q].y));
-        uint4 vv = make_uint4(0, 0, 0, 0);  // dd = l32 >= D: zero rows of V^T
-        if (l32 < D) vv = *reinterpret_cast<const uint4*>(Vt + (q * D + l32) * VST + (((2 * (2 * kb + st) + h) ^ vt_swz(l32)) << 3));
-        vf[q] = __builtin_bit_cast(bf16x8, vv);
-      }
-#pragma unroll
-      for (int j = JS; j < NP; ++j) o = mfma(vf[QA[j]], pf[QB[j]], o);
-    }
+  o = pv_terms<D, F16, ONE>(s, Vt, l32, h, o);
 
   const float oscale = F16 ? rinv * iq * (1.f / 16384.f) : rinv;
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] *= oscale;
-  // scatter: query 32*wid + l32 (lane column), dd rows (r&3) + 8(r>>2) + 4h
+  // scatter: query 32*wid + l32 (lane column)
   const int qi = 32 * wid + l32;
   const int qpos = key_start + qi;
-  if (qi < Kwin && qpos >= query_start) {
-    float* dst = out + (long long)rows[qi] * C + head * D;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int dd = 8 * g + 4 * h;
-      if (dd + 3 < D) {
-        *reinterpret_cast<float4*>(dst + dd) = make_float4(o[4 * g + 0], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]);
-      }
-    }
-  }
-}
-
-
-// window_attn_split_kernel<D, true> as a software pipeline over consecutive (window, head) items (window-major:
-// all heads of a window back to back): a workgroup owns `ipw` consecutive items and, while it computes item i from
-// LDS buffer i & 1, has item i + 1's row indices and q / k / v slices in flight into registers, split into the
-// other buffer after item i's MFMAs -- the row gathers (the old kernel's whole latency: one item per workgroup,
-// gather -> barrier -> compute -> store) overlap the compute.  Same arithmetic, same term order: outputs are bit
-// for bit those of window_attn_split_kernel (test_window_attention_seq_bitwise).
-template <int D>
-__global__ void __launch_bounds__(256, 2)
-window_attn_seq_kernel(const float* __restrict__ qkv, const int* __restrict__ order, const int* __restrict__ win,
-                       int Kwin, int C, float scale, float* __restrict__ out,
-                       const unsigned long long* __restrict__ qkv_amax, unsigned qkv_tag, int items, int ipw) {
-  typedef _Float16 bf16x8 __attribute__((ext_vector_type(8)));
-  constexpr int NT = 2;
-  constexpr int KD = D == 16 ? 16 : 32;
-  constexpr int NKS = KD / 16;
-  constexpr int QROW = KD == 16 ? 48 : 64;
-  constexpr int VST = 136;
-  constexpr int QK_BYTES = NT * KMAX * QROW;
-  constexpr int V_BYTES = NT * D * VST * 2;
-  constexpr int BUF = QK_BYTES + V_BYTES;
-  constexpr int CH = D / 4;
-  constexpr int NK = (KMAX * CH + 255) / 256;         // K float4 per thread
-  constexpr int NV = ((KMAX / 2) * CH + 255) / 256;   // V key pairs per thread
-  float sq = 1.f, iq = 1.f;
-  {
-    const float m = sfx::read_amax(qkv_amax, qkv_tag);
-    int e = 0;
-    if (m > 0.f && m <= 3.4028235e38f) {
-      (void)frexpf(m, &e);
-      e = 15 - e;
-      e = e > 126 ? 126 : (e < -126 ? -126 : e);
-    }
-    sq = ldexpf(1.f, e);
-    iq = ldexpf(1.f, -e);
-  }
-  __shared__ __attribute__((aligned(16))) char lds[2 * BUF];
-  auto qk_off = [](int r, int c) -> int {
-    return KD == 16 ? r * 48 + c * 16 : r * 64 + (((c ^ (r >> 2)) & 3) << 4);
-  };
-  const int heads = C / D;
-  const int nb = (int)gridDim.x;
-  const int L = (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8);
-  const int i0 = L * ipw, i1 = min(items, i0 + ipw);
-  if (i0 >= i1) return;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, h = lane >> 5, l32 = lane & 31;
-  const long long ld = 3ll * C;
-  if (D < KD)  // K columns D..KD-1 of both buffers: zero once
-    for (int rr = tid; rr < 2 * NT * KMAX; rr += 256) {
-      const int b = rr / (NT * KMAX), r2 = rr - b * NT * KMAX;
-      *reinterpret_cast<uint4*>(lds + b * BUF + qk_off(r2, D / 8)) = make_uint4(0, 0, 0, 0);
-    }
-
-  // ---- one item's gathered slices (registers) ----
-  float4 kv[NK], vv0[NV], vv1[NV], qv[NKS][2];
-  int qrow = -1;  // this lane's query point (output row) of the staged item
-  auto fetch = [&](int it) {
-    const int w = it / heads, head = it - w * heads;
-    const int key_start = win[2 * w];
-#pragma unroll
-    for (int j = 0; j < NK; ++j) {
-      const int e = tid + 256 * j;
-      const int row = e / CH, ch = e - row * CH;
-      kv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row < Kwin && e < KMAX * CH) {
-        const int src = order[key_start + row];
-        kv[j] = *reinterpret_cast<const float4*>(qkv + (long long)src * ld + C + head * D + 4 * ch);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const int e = tid + 256 * j;
-      const int kp = e / CH, ch = e - kp * CH;
-      vv0[j] = vv1[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (e < (KMAX / 2) * CH) {
-        const int r0 = 2 * kp;
-        if (r0 < Kwin)
-          vv0[j] = *reinterpret_cast<const float4*>(qkv + (long long)order[key_start + r0] * ld + 2 * C + head * D + 4 * ch);
-        if (r0 + 1 < Kwin)
-          vv1[j] = *reinterpret_cast<const float4*>(qkv + (long long)order[key_start + r0 + 1] * ld + 2 * C + head * D +
-                                                    4 * ch);
-      }
-    }
-    const int qi = 32 * wid + l32;
-    qrow = qi < Kwin ? order[key_start + qi] : -1;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const int d0 = 16 * ks + 8 * h;
-      qv[ks][0] = qv[ks][1] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (qrow >= 0 && d0 < D) {
-        const float* qp = qkv + (long long)qrow * ld + head * D + d0;
-        qv[ks][0] = *reinterpret_cast<const float4*>(qp);
-        if (d0 + 4 < D) qv[ks][1] = *reinterpret_cast<const float4*>(qp + 4);
-      }
-    }
-  };
-  // ---- split into LDS buffer b (K, V^T) and the q fragments ----
-  bf16x8 qf[NKS][NT];
-  int qrow_s = -1;
-  auto stage = [&](int b) {
-    char* Ks = lds + b * BUF;
-    unsigned short* Vt = reinterpret_cast<unsigned short*>(lds + b * BUF + QK_BYTES);
-#pragma unroll
-    for (int j = 0; j < NK; ++j) {
-      const int e = tid + 256 * j;
-      if (e < KMAX * CH) {
-        const int row = e / CH, ch = e - row * CH;
-        uint2 t[NT];
-        sfx::split2h(kv[j], sq, t);
-        const int o = qk_off(row, ch >> 1) + ((ch & 1) << 3);
-#pragma unroll
-        for (int q = 0; q < NT; ++q) *reinterpret_cast<uint2*>(Ks + q * KMAX * QROW + o) = t[q];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const int e = tid + 256 * j;
-      if (e < (KMAX / 2) * CH) {
-        const int kp = e / CH, ch = e - kp * CH;
-        const int row = 2 * kp;
-        uint2 t0[NT], t1[NT];
-        sfx::split2h(vv0[j], sq, t0);
-        sfx::split2h(vv1[j], sq, t1);
-        const int kk = row & 15;
-        const int pos = (row & ~15) + 8 * ((kk >> 2) & 1) + (((kk >> 3) << 2) | (kk & 3));
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-          unsigned* vt = reinterpret_cast<unsigned*>(Vt + (q * D + 4 * ch) * VST + (pos ^ (8 * vt_swz(4 * ch))));
-          vt[0] = (t0[q].x & 0xffffu) | (t1[q].x << 16);
-          vt[VST / 2] = (t0[q].x >> 16) | (t1[q].x & 0xffff0000u);
-          vt[VST] = (t0[q].y & 0xffffu) | (t1[q].y << 16);
-          vt[3 * VST / 2] = (t0[q].y >> 16) | (t1[q].y & 0xffff0000u);
-        }
-      }
-    }
-    const float qs = scale * 1.4426950408889634f;
-    typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      float4 a = qv[ks][0], bb = qv[ks][1];
-      a.x *= qs; a.y *= qs; a.z *= qs; a.w *= qs;
-      bb.x *= qs; bb.y *= qs; bb.z *= qs; bb.w *= qs;
-      uint2 ta[NT], tb[NT];
-      sfx::split2h(a, sq, ta);
-      sfx::split2h(bb, sq, tb);
-#pragma unroll
-      for (int q = 0; q < NT; ++q) qf[ks][q] = __builtin_bit_cast(bf16x8, (uintx4){ta[q].x, ta[q].y, tb[q].x, tb[q].y});
-    }
-    qrow_s = qrow;
-  };
-
-  fetch(i0);
-  stage(0);
-  __syncthreads();
-  constexpr int QA[3] = {1, 0, 0}, QB[3] = {0, 1, 0};
-  auto mfma = [](const bf16x8& a, const bf16x8& b, floatx16 c) -> floatx16 {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  };
-#pragma unroll 1
-  for (int it = i0; it < i1; ++it) {
-    const int b = (it - i0) & 1;
-    const int w = it / heads, head = it - w * heads;
-    const int key_start = win[2 * w], query_start = win[2 * w + 1];
-    if (it + 1 < i1) fetch(it + 1);  // next item's slices in flight during this item's compute
-    const char* Ks = lds + b * BUF;
-    const unsigned short* Vt = reinterpret_cast<const unsigned short*>(lds + b * BUF + QK_BYTES);
-    floatx16 sacc[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[kb][r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        bf16x8 kf[NT];
-#pragma unroll
-        for (int q = 0; q < NT; ++q)
-          kf[q] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(
-                                                 Ks + q * KMAX * QROW + qk_off(kb * 32 + l32, 2 * ks + h)));
-#pragma unroll
-        for (int j = 0; j < 3; ++j) sacc[kb] = mfma(kf[QA[j]], qf[ks][QB[j]], sacc[kb]);
-      }
-    }
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[kb][r] = sacc[kb][r] * iq * iq;
-    if (Kwin < KMAX) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          if (key >= Kwin) sacc[kb][r] = -INFINITY;
-        }
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = __builtin_amdgcn_exp2f(sacc[kb][r] - mx);
-        sacc[kb][r] = e;
-        sum += e;
-      }
-    sum += __shfl_xor(sum, 32, 64);
-    const float rinv = 1.f / sum;
-    floatx16 o;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        uint2 a[NT], bb[NT];
-        sfx::split2h(make_float4(sacc[kb][8 * st + 0], sacc[kb][8 * st + 1], sacc[kb][8 * st + 2], sacc[kb][8 * st + 3]),
-                     16384.f, a);
-        sfx::split2h(make_float4(sacc[kb][8 * st + 4], sacc[kb][8 * st + 5], sacc[kb][8 * st + 6], sacc[kb][8 * st + 7]),
-                     16384.f, bb);
-        bf16x8 pf[NT], vf[NT];
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-          pf[q] = __builtin_bit_cast(bf16x8, make_uint4(a[q].x, a[q].y, bb[q].x, bb[q].y));
-          uint4 v4 = make_uint4(0, 0, 0, 0);
-          if (l32 < D) v4 = *reinterpret_cast<const uint4*>(Vt + (q * D + l32) * VST + (((2 * (2 * kb + st) + h) ^ vt_swz(l32)) << 3));
-          vf[q] = __builtin_bit_cast(bf16x8, v4);
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o = mfma(vf[QA[j]], pf[QB[j]], o);
-      }
-    const float oscale = rinv * iq * (1.f / 16384.f);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] *= oscale;
-    const int qi = 32 * wid + l32;
-    const int qpos = key_start + qi;
-    if (qi < Kwin && qpos >= query_start) {
-      float* dst = out + (long long)qrow_s * C + head * D;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dd = 8 * g + 4 * h;
-        if (dd + 3 < D) *reinterpret_cast<float4*>(dst + dd) = make_float4(o[4 * g + 0], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]);
-      }
-    }
-    if (it + 1 < i1) stage(b ^ 1);
-    __syncthreads();
-  }
+  if (qi < Kwin && qpos >= query_start) store_ot<D>(out + (long long)rows[qi] * C + head * D, o, h);
 }
 
 
@@ -988,47 +542,22 @@ __global__ void __launch_bounds__(256, D == 16 ? 4 : 3)
 window_attn_split_flash_kernel(const float* __restrict__ qkv, const int* __restrict__ order,
                                const int* __restrict__ win3, int qblocks, int C, float scale, float* __restrict__ out,
                                const unsigned long long* __restrict__ qkv_amax, unsigned qkv_tag, int nwin) {
-  typedef typename std::conditional<F16, _Float16, __bf16>::type elem_t;
-  typedef elem_t bf16x8 __attribute__((ext_vector_type(8)));  // (fragment type: bf16 or fp16 terms)
-  constexpr int NT = F16 ? 2 : 3;            // terms per operand
+  constexpr int NT = nterms(F16);           // terms per operand
   constexpr int KD = D == 16 ? 16 : 32;
   constexpr int NKS = KD / 16;
-  constexpr int QROW = KD == 16 ? 48 : 64;  // bytes per Q/K term row
-  constexpr int VST = 136;                  // V^T row stride (16-bit elements)
-  constexpr int QK_BYTES = NT * KMAX * QROW;
+  constexpr int QK_BYTES = NT * KMAX * row_bytes(KD);
   constexpr int V_BYTES = NT * D * VST * 2;
   // operand scales (F16): qkv by sq, probabilities by 2^14
   float sq = 1.f, iq = 1.f;
-  if constexpr (F16) {
-    const float m = sfx::read_amax(qkv_amax, qkv_tag);
-    int e = 0;
-    if (m > 0.f && m <= 3.4028235e38f) {
-      (void)frexpf(m, &e);
-      e = 15 - e;
-      e = e > 126 ? 126 : (e < -126 ? -126 : e);
-    }
-    sq = ldexpf(1.f, e);
-    iq = ldexpf(1.f, -e);
-  }
-  auto split = [&](float4 v, float sc, uint2 (&t)[NT]) {
-    if constexpr (F16) sfx::split2h(v, sc, t); else sfx::split3(v, t);
-  };
+  if constexpr (F16) sq = sfx::pow2_scale(sfx::read_amax(qkv_amax, qkv_tag), iq);
   __shared__ __attribute__((aligned(16))) char lds[QK_BYTES + V_BYTES];
   __shared__ int rows[KMAX];   // keys of the current block
   __shared__ int qrows[KMAX];  // this workgroup's queries
   char* Ks = lds;
   unsigned short* Vt = reinterpret_cast<unsigned short*>(lds + QK_BYTES);
-  // byte offset of 16-byte chunk c of term row r
-  auto qk_off = [](int r, int c) -> int {
-    return KD == 16 ? r * 48 + c * 16 : r * 64 + (((c ^ (r >> 2)) & 3) << 4);
-  };
 
-  // XCD-aware numbering over a 1-D grid padded to a multiple of 8: consecutive blocks go round-robin to the 8
-  // XCDs, so logical id L = xcd * (grid / 8) + slot puts all heads of a window on one XCD back to back -- the
-  // 128-byte qkv lines its heads share (d = 16: two heads per line) are fetched from HBM once into that L2.
   const int heads = C / D;
-  const int nb = (int)gridDim.x;
-  const int L = (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8);
+  const int L = xcd_logical_id();
   if (L >= nwin * qblocks * heads) return;
   const int wq = L / heads, head = L - wq * heads;
   const int w = wq / qblocks, qb = wq - w * qblocks;
@@ -1039,47 +568,10 @@ window_attn_split_flash_kernel(const float* __restrict__ qkv, const int* __restr
   const long long ld = 3ll * C;
 
   if (tid < KMAX) qrows[tid] = q0 + tid < count ? order[key_start + q0 + tid] : -1;
-  // zero padding: K columns D..KD-1 (never written by the staging below)
-  if (D < KD)
-    for (int rr = tid; rr < NT * KMAX; rr += 256)  // term rows, term-major
-      *reinterpret_cast<uint4*>(Ks + qk_off(rr, D / 8)) = make_uint4(0, 0, 0, 0);
+  zero_row_pad<D, KD>(Ks, NT * KMAX, tid);
   __syncthreads();
-  // gather + split, one matrix at a time (wave-uniform paths): q, k rows as KMAX x D/4 float4; v as
-  // key pairs x D/4 float4 so the transposed V^T writes are whole dwords (keys 2m, 2m+1 are adjacent
-  // in the permuted order)
-  constexpr int CH = D / 4;
-  typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-  // this lane's query slices (B operand of S^T = K Q^T): dd = 16 ks + 8h + j, zero past D
-  bf16x8 qf[NKS][NT];
-  {
-    const int src = qrows[32 * wid + l32];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const int d0 = 16 * ks + 8 * h;
-      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-      if (src >= 0 && d0 < D) {
-        const float* qp = qkv + (long long)src * ld + head * D + d0;
-        a = *reinterpret_cast<const float4*>(qp);
-        if (d0 + 4 < D) b = *reinterpret_cast<const float4*>(qp + 4);
-      }
-      // scale * log2(e) folded into q: the softmax exponentials are plain exp2
-      const float qs = scale * 1.4426950408889634f;
-      a.x *= qs; a.y *= qs; a.z *= qs; a.w *= qs;
-      b.x *= qs; b.y *= qs; b.z *= qs; b.w *= qs;
-      uint2 ta[NT], tb[NT];
-      split(a, sq, ta);  // (|q * qs| <= |q|: the qkv bound holds)
-      split(b, sq, tb);
-#pragma unroll
-      for (int q = 0; q < NT; ++q) qf[ks][q] = __builtin_bit_cast(bf16x8, (uintx4){ta[q].x, ta[q].y, tb[q].x, tb[q].y});
-    }
-  }
-  // term products, smallest first
-  constexpr int NP = F16 ? 3 : 6;
-  constexpr int QA[6] = {F16 ? 1 : 2, F16 ? 0 : 1, 0, 1, 0, 0}, QB[6] = {0, 1, F16 ? 0 : 2, 0, 1, 0};
-  auto mfma = [](const bf16x8& a, const bf16x8& b, floatx16 c) -> floatx16 {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  };
+  frag_t<F16> qf[NKS][NT];
+  fwd_query_frags<D, F16, NKS>(qkv, qrows[32 * wid + l32], ld, head, h, scale, sq, qf);
   float m_run = -INFINITY, l_run = 0.f;
   floatx16 o;
 #pragma unroll
@@ -1090,16 +582,20 @@ window_attn_split_flash_kernel(const float* __restrict__ qkv, const int* __restr
     __syncthreads();  // the previous block's fragment reads are done
     if (tid < KMAX) rows[tid] = tid < nk ? order[key_start + k0 + tid] : -1;
     __syncthreads();
+    // The K-row and V^T staging of fwd_stage_kv, written out: through stage_row / stage_pair (or any smaller helper
+    // for the offset or the key-pair permutation) the d = 16 instantiations, compiled at the 128-VGPR limit, spill
+    // 12 / 8 B more per lane than the parent and run 4 % / 1 % slower
+    constexpr int CH = D / 4;
     for (int e = tid; e < KMAX * CH; e += 256) {
       const int row = e / CH, ch = e - row * CH;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       const int src = rows[row];
       if (src >= 0) v = *reinterpret_cast<const float4*>(qkv + (long long)src * ld + C + head * D + 4 * ch);
       uint2 t[NT];
-      split(v, sq, t);
-      const int o = qk_off(row, ch >> 1) + ((ch & 1) << 3);
+      split<F16>(v, sq, t);
+      const int o = row_off<KD>(row, ch >> 1) + ((ch & 1) << 3);
 #pragma unroll
-      for (int q = 0; q < NT; ++q) *reinterpret_cast<uint2*>(Ks + q * KMAX * QROW + o) = t[q];
+      for (int q = 0; q < NT; ++q) *reinterpret_cast<uint2*>(Ks + q * KMAX * row_bytes(KD) + o) = t[q];
     }
     for (int e = tid; e < (KMAX / 2) * CH; e += 256) {
       const int kp = e / CH, ch = e - kp * CH;
@@ -1109,9 +605,9 @@ window_attn_split_flash_kernel(const float* __restrict__ qkv, const int* __restr
       if (s0 >= 0) v0 = *reinterpret_cast<const float4*>(qkv + (long long)s0 * ld + 2 * C + head * D + 4 * ch);
       if (s1 >= 0) v1 = *reinterpret_cast<const float4*>(qkv + (long long)s1 * ld + 2 * C + head * D + 4 * ch);
       uint2 t0[NT], t1[NT];
-      split(v0, sq, t0);
-      split(v1, sq, t1);
-      const int kk = row & 15;  // even: keys row, row + 1 land on adjacent positions
+      split<F16>(v0, sq, t0);
+      split<F16>(v1, sq, t1);
+      const int kk = row & 15;  // even: keys row, row + 1 land on adjacent positions (as stage_pair)
       const int pos = (row & ~15) + 8 * ((kk >> 2) & 1) + (((kk >> 3) << 2) | (kk & 3));
 #pragma unroll
       for (int q = 0; q < NT; ++q) {
@@ -1124,103 +620,29 @@ window_attn_split_flash_kernel(const float* __restrict__ qkv, const int* __restr
     }
     __syncthreads();
 
-    // S^T[key][query] for this wave's 32 queries, 4 key blocks of 32
     floatx16 s[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        bf16x8 kf[NT];
-#pragma unroll
-        for (int q = 0; q < NT; ++q)
-          kf[q] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(
-                                                 Ks + q * KMAX * QROW + qk_off(kb * 32 + l32, 2 * ks + h)));
-#pragma unroll
-        for (int j = 0; j < NP; ++j) s[kb] = mfma(kf[QA[j]], qf[ks][QB[j]], s[kb]);
-      }
-    }
-    if constexpr (F16) {  // S was formed from sq-scaled q and k
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[kb][r] = s[kb][r] * iq * iq;
-    }
-    // online softmax over this key block (register axis + the other half-wave); keys >= nk are padding
-    if (nk < KMAX) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          if (key >= nk) s[kb][r] = -INFINITY;
-        }
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    mx = fmaxf(mx, m_run);  // finite: every block holds at least one key
+    fwd_scores<KD, F16, false, NKS>(Ks, qf, l32, h, iq, s);
+    // online softmax over this key block; keys >= nk are padding
+    if (nk < KMAX) score_mask(s, h, nk);
+    const float mx = fmaxf(score_max(s), m_run);  // finite: every block holds at least one key
     const float corr = __builtin_amdgcn_exp2f(m_run - mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = __builtin_amdgcn_exp2f(s[kb][r] - mx);
-        s[kb][r] = e;
-        sum += e;
-      }
-    sum += __shfl_xor(sum, 32, 64);
-    l_run = l_run * corr + sum;
+    l_run = l_run * corr + score_exp<true>(s, mx);
     m_run = mx;
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[r] *= corr;
-
-    // O^T[dd][query] += sum_key V^T[dd][key] P^T[key][query]
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        uint2 a[NT], b[NT];
-        // unnormalised exp values (0, 1] (F16: scaled by 2^14); 1/sum is applied to O
-        split(make_float4(s[kb][8 * st + 0], s[kb][8 * st + 1], s[kb][8 * st + 2], s[kb][8 * st + 3]), 16384.f, a);
-        split(make_float4(s[kb][8 * st + 4], s[kb][8 * st + 5], s[kb][8 * st + 6], s[kb][8 * st + 7]), 16384.f, b);
-        bf16x8 pf[NT], vf[NT];
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-          pf[q] = __builtin_bit_cast(bf16x8, make_uint4(a[q].x, a[q].y, b[q].x, b[q].y));
-          uint4 vv = make_uint4(0, 0, 0, 0);  // dd = l32 >= D: zero rows of V^T
-          if (l32 < D) vv = *reinterpret_cast<const uint4*>(Vt + (q * D + l32) * VST + (((2 * (2 * kb + st) + h) ^ vt_swz(l32)) << 3));
-          vf[q] = __builtin_bit_cast(bf16x8, vv);
-        }
-#pragma unroll
-        for (int j = 0; j < NP; ++j) o = mfma(vf[QA[j]], pf[QB[j]], o);
-      }
+    o = pv_terms<D, F16, false>(s, Vt, l32, h, o);
   }  // key blocks
 
   const float rinv = 1.f / l_run;
   const float oscale = F16 ? rinv * iq * (1.f / 16384.f) : rinv;
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] *= oscale;
-  // scatter: query 32*wid + l32 (lane column), dd rows (r&3) + 8(r>>2) + 4h
+  // scatter: query q0 + 32*wid + l32 (lane column)
   const int qi = q0 + 32 * wid + l32;
-  if (qi < count && key_start + qi >= query_start) {
-    float* dst = out + (long long)qrows[32 * wid + l32] * C + head * D;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int dd = 8 * g + 4 * h;
-      if (dd + 3 < D) {
-        *reinterpret_cast<float4*>(dst + dd) = make_float4(o[4 * g + 0], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]);
-      }
-    }
-  }
+  if (qi < count && key_start + qi >= query_start)
+    store_ot<D>(out + (long long)qrows[32 * wid + l32] * C + head * D, o, h);
 }
+
 
 
 // ---- backward (training, configs C/D) ---------------------------------------------------------------
@@ -1280,51 +702,14 @@ window_attn_bwd_kernel(const float* __restrict__ qkv, const int* __restrict__ or
   // ---------------- phase A: this wave's 32 queries on the lane columns ----------------
   const int qi = 32 * wid + l32;
   floatx16 s[4];
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
   {
-    const float* qrow = &Qs[qi * DP + h * HALF];
-#pragma unroll
-    for (int c = 0; c < HALF / 4; ++c) {
-      const float4 qv = *reinterpret_cast<const float4*>(qrow + 4 * c);
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        const float4 kv = *reinterpret_cast<const float4*>(&Ks[(kb * 32 + l32) * DP + h * HALF + 4 * c]);
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.x, qv.x, s[kb], 0, 0, 0);
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.y, qv.y, s[kb], 0, 0, 0);
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.z, qv.z, s[kb], 0, 0, 0);
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.w, qv.w, s[kb], 0, 0, 0);
-      }
-    }
+    float4 qv[HALF / 4];
+    exact_load_half<HALF>(&Qs[qi * DP], h, qv);
+    exact_scores<HALF, DP>(Ks, qv, l32, h, s);
   }
-  if (Kwin < KMAX) {
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (key >= Kwin) s[kb][r] = -INFINITY;
-      }
-  }
-  float mx = -INFINITY;
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float e = __expf(s[kb][r] - mx);
-      s[kb][r] = e;
-      sum += e;
-    }
-  sum += __shfl_xor(sum, 32, 64);
-  const float rinv = 1.f / sum;
+  if (Kwin < KMAX) score_mask(s, h, Kwin);
+  const float mx = score_max(s);
+  const float rinv = 1.f / score_exp<false>(s, mx);
 #pragma unroll
   for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
@@ -1336,14 +721,10 @@ window_attn_bwd_kernel(const float* __restrict__ qkv, const int* __restrict__ or
   const float* vcol = &Vs[4 * h * DP + l32];
   const float* kcol = &Ks[4 * h * DP + l32];
 #pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int st = 0; st < 16; ++st)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(vcol[(kb * 32 + (st & 3) + 8 * (st >> 2)) * DP], s[kb][st], acc, 0, 0,
-                                                 0);
+  for (int kb = 0; kb < 4; ++kb) acc = exact_col_mfma<DP>(vcol, kb, s[kb], acc);
   float delta = 0.f;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) delta += acc[r] * dOs[qi * DP + (r & 3) + 8 * (r >> 2) + 4 * h];
+  for (int r = 0; r < 16; ++r) delta += acc[r] * dOs[qi * DP + score_key(0, r, h)];
   delta += __shfl_xor(delta, 32, 64);
   // per key block: dP^T = V dO^T, dS^T = P^T (dP^T - Delta), dQ^T += K^T dS^T
 #pragma unroll
@@ -1355,30 +736,20 @@ window_attn_bwd_kernel(const float* __restrict__ qkv, const int* __restrict__ or
 #pragma unroll
     for (int r = 0; r < 16; ++r) dp[r] = 0.f;
 #pragma unroll
-    for (int c = 0; c < HALF / 4; ++c) {
-      const float4 gv = *reinterpret_cast<const float4*>(grow + 4 * c);
-      const float4 vv = *reinterpret_cast<const float4*>(&Vs[(kb * 32 + l32) * DP + h * HALF + 4 * c]);
-      dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.x, gv.x, dp, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.y, gv.y, dp, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.z, gv.z, dp, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.w, gv.w, dp, 0, 0, 0);
-    }
+    for (int c = 0; c < HALF / 4; ++c)
+      dp = exact_mfma4(*reinterpret_cast<const float4*>(&Vs[(kb * 32 + l32) * DP + h * HALF + 4 * c]),
+                       *reinterpret_cast<const float4*>(grow + 4 * c), dp);
 #pragma unroll
     for (int st = 0; st < 16; ++st) {
       const float ds = s[kb][st] * (dp[st] - delta);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kcol[(kb * 32 + (st & 3) + 8 * (st >> 2)) * DP], ds, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kcol[score_key(kb, st, 0) * DP], ds, acc, 0, 0, 0);
     }
   }
   const int qpos = key_start + qi;
   if (qi < Kwin && qpos >= query_start) {
-    float* dst = dqkv + (long long)rows[qi] * ld + head * D;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int dd = 8 * g + 4 * h;
-      if (dd + 3 < D)
-        *reinterpret_cast<float4*>(dst + dd) =
-            make_float4(acc[4 * g + 0] * scale, acc[4 * g + 1] * scale, acc[4 * g + 2] * scale, acc[4 * g + 3] * scale);
-    }
+    for (int r = 0; r < 16; ++r) acc[r] *= scale;
+    store_ot<D>(dqkv + (long long)rows[qi] * ld + head * D, acc, h);
   }
   if (h == 0) {
     st_max[qi] = mx;
@@ -1410,22 +781,16 @@ window_attn_bwd_kernel(const float* __restrict__ qkv, const int* __restrict__ or
       const float4 gv = *reinterpret_cast<const float4*>(grw + 4 * c);
       const float4 kv = *reinterpret_cast<const float4*>(krow + 4 * c);
       const float4 vv = *reinterpret_cast<const float4*>(vrow + 4 * c);
-      sb = __builtin_amdgcn_mfma_f32_32x32x2f32(qv.x, kv.x, sb, 0, 0, 0);
-      sb = __builtin_amdgcn_mfma_f32_32x32x2f32(qv.y, kv.y, sb, 0, 0, 0);
-      sb = __builtin_amdgcn_mfma_f32_32x32x2f32(qv.z, kv.z, sb, 0, 0, 0);
-      sb = __builtin_amdgcn_mfma_f32_32x32x2f32(qv.w, kv.w, sb, 0, 0, 0);
-      pb = __builtin_amdgcn_mfma_f32_32x32x2f32(gv.x, vv.x, pb, 0, 0, 0);
-      pb = __builtin_amdgcn_mfma_f32_32x32x2f32(gv.y, vv.y, pb, 0, 0, 0);
-      pb = __builtin_amdgcn_mfma_f32_32x32x2f32(gv.z, vv.z, pb, 0, 0, 0);
-      pb = __builtin_amdgcn_mfma_f32_32x32x2f32(gv.w, vv.w, pb, 0, 0, 0);
+      sb = exact_mfma4(qv, kv, sb);
+      pb = exact_mfma4(gv, vv, pb);
     }
     // sb[r] = S[q][kk], pb[r] = dP[q][kk] for q = qb*32 + (r&3) + 8(r>>2) + 4h
 #pragma unroll
     for (int st = 0; st < 16; ++st) {
-      const int q = qb * 32 + (st & 3) + 8 * (st >> 2) + 4 * h;
+      const int q = score_key(qb, st, h);
       const float P = key_ok ? __expf(sb[st] - st_max[q]) * st_rinv[q] : 0.f;
       const float dS = P * (pb[st] - st_delta[q]);
-      const int qo = (qb * 32 + (st & 3) + 8 * (st >> 2)) * DP;  // + 4h folded into gcol / qcol
+      const int qo = score_key(qb, st, 0) * DP;  // + 4h folded into gcol / qcol
       dv = __builtin_amdgcn_mfma_f32_32x32x2f32(gcol[qo], P, dv, 0, 0, 0);
       dk = __builtin_amdgcn_mfma_f32_32x32x2f32(qcol[qo], dS, dk, 0, 0, 0);
     }
@@ -1437,7 +802,7 @@ window_attn_bwd_kernel(const float* __restrict__ qkv, const int* __restrict__ or
   __syncthreads();  // all waves done reading Q/K/V/dO
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int dd = (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int dd = score_key(0, r, h);
     Qs[kk * DP + dd] = dk[r];
     Vs[kk * DP + dd] = dv[r];
   }
@@ -1478,21 +843,6 @@ window_attn_bwd_kernel(const float* __restrict__ qkv, const int* __restrict__ or
 // exact kernel; recomputing S and dP in the key pass is what keeps both passes' contractions on the register axis.
 // LDS per item: row images [2 terms][128][KD] (as the forward's K image) and transposed images [2][D][136] with the
 // keys (queries) of each 16-group in the B-operand register order (as the forward's V^T).
-template <int KD>
-__device__ __forceinline__ int bwd_row_off(int r, int c) {  // byte offset of 16-byte chunk c of term row r
-  return KD == 16 ? r * 48 + c * 16 : r * 64 + (((c ^ (r >> 2)) & 3) << 4);
-}
-// power of two s with m * s in [2^14, 2^15) (1 for m == 0 or non-finite m); inv = 1 / s
-__device__ __forceinline__ float bwd_pow2(float m, float& inv) {
-  int e = 0;
-  if (m > 0.f && m <= 3.4028235e38f) {
-    (void)frexpf(m, &e);
-    e = 15 - e;
-    e = e > 126 ? 126 : (e < -126 ? -126 : e);
-  }
-  inv = ldexpf(1.f, -e);
-  return ldexpf(1.f, e);
-}
 __device__ __forceinline__ float amax4(float4 v) {
   return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
 }
@@ -1515,83 +865,6 @@ __device__ __forceinline__ float4 bwd_wg_max4(float4 m, float4* red) {
   }
   return r;
 }
-// two fp16 terms of 8 scaled values -> B-operand fragments
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void bwd_frag(float4 a, float4 b, float s, f16x8 (&f)[2]) {
-  uint2 ta[2], tb[2];
-  sfx::split2h(a, s, ta);
-  sfx::split2h(b, s, tb);
-#pragma unroll
-  for (int t = 0; t < 2; ++t) f[t] = __builtin_bit_cast(f16x8, make_uint4(ta[t].x, ta[t].y, tb[t].x, tb[t].y));
-}
-// ONE (sfx_set_precision(1), the reference's autocast class): the leading product only
-template <bool ONE = false>
-__device__ __forceinline__ floatx16 mfma3(const f16x8 (&a)[2], const f16x8 (&b)[2], floatx16 c) {
-  if constexpr (ONE) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], c, 0, 0, 0);  // smallest first
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], c, 0, 0, 0);
-}
-// a lane's 8 (or fewer, zero-padded past D) values of row `src`, columns d0 .. d0 + 7
-template <int D>
-__device__ __forceinline__ void bwd_load8(const float* p, int d0, bool ok, float4& a, float4& b) {
-  a = make_float4(0.f, 0.f, 0.f, 0.f);
-  b = a;
-  if (ok && d0 < D) {
-    a = *reinterpret_cast<const float4*>(p + d0);
-    if (d0 + 4 < D) b = *reinterpret_cast<const float4*>(p + d0 + 4);
-  }
-}
-// row image + transposed image of a pair of rows (2p, 2p + 1), float4 column chunk ch, terms of x * s
-template <int D, int KD>
-__device__ __forceinline__ void bwd_stage_pair(char* rimg, unsigned short* timg, int row, int ch, float4 v0, float4 v1,
-                                               float s) {
-  constexpr int QROW = KD == 16 ? 48 : 64, VST = 136;
-  uint2 t0[2], t1[2];
-  sfx::split2h(v0, s, t0);
-  sfx::split2h(v1, s, t1);
-  const int o0 = bwd_row_off<KD>(row, ch >> 1) + ((ch & 1) << 3);
-  const int o1 = bwd_row_off<KD>(row + 1, ch >> 1) + ((ch & 1) << 3);
-  const int kk = row & 15;  // even: rows row, row + 1 land on adjacent positions
-  const int pos = (row & ~15) + 8 * ((kk >> 2) & 1) + (((kk >> 3) << 2) | (kk & 3));
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    *reinterpret_cast<uint2*>(rimg + q * KMAX * QROW + o0) = t0[q];
-    *reinterpret_cast<uint2*>(rimg + q * KMAX * QROW + o1) = t1[q];
-    unsigned* vt = reinterpret_cast<unsigned*>(timg + (q * D + 4 * ch) * VST + (pos ^ (8 * vt_swz(4 * ch))));
-    vt[0] = (t0[q].x & 0xffffu) | (t1[q].x << 16);
-    vt[VST / 2] = (t0[q].x >> 16) | (t1[q].x & 0xffff0000u);
-    vt[VST] = (t0[q].y & 0xffffu) | (t1[q].y << 16);
-    vt[3 * VST / 2] = (t0[q].y >> 16) | (t1[q].y & 0xffff0000u);
-  }
-}
-template <int KD>
-__device__ __forceinline__ void bwd_stage_row(char* rimg, int row, int ch, float4 v, float s) {
-  constexpr int QROW = KD == 16 ? 48 : 64;
-  uint2 t[2];
-  sfx::split2h(v, s, t);
-  const int o = bwd_row_off<KD>(row, ch >> 1) + ((ch & 1) << 3);
-#pragma unroll
-  for (int q = 0; q < 2; ++q) *reinterpret_cast<uint2*>(rimg + q * KMAX * QROW + o) = t[q];
-}
-template <int KD>
-__device__ __forceinline__ void bwd_row_frag(const char* rimg, int row, int c, f16x8 (&f)[2]) {
-  constexpr int QROW = KD == 16 ? 48 : 64;
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-    f[q] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(rimg + q * KMAX * QROW + bwd_row_off<KD>(row, c)));
-}
-// A fragment of a transposed image: lane row dd = l32 (zero past D), 8 keys of 16-step `step` from half h
-template <int D>
-__device__ __forceinline__ void bwd_tr_frag(const unsigned short* timg, int l32, int step, int h, f16x8 (&f)[2]) {
-  constexpr int VST = 136;
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (l32 < D) v = *reinterpret_cast<const uint4*>(timg + (q * D + l32) * VST + (((2 * step + h) ^ vt_swz(l32)) << 3));
-    f[q] = __builtin_bit_cast(f16x8, v);
-  }
-}
 
 template <int D, bool ONE = false>
 __global__ void __launch_bounds__(256, 3)
@@ -1599,7 +872,7 @@ window_attn_bwd_q_kernel(const float* __restrict__ qkv, const int* __restrict__ 
                          int Kwin, int C, float scale, const float* __restrict__ attn_out,
                          const float* __restrict__ dout, float* __restrict__ dqkv, float4* __restrict__ stats,
                          int nwin) {
-  constexpr int KD = D == 16 ? 16 : 32, NKS = KD / 16, QROW = KD == 16 ? 48 : 64, VST = 136;
+  constexpr int KD = D == 16 ? 16 : 32, NKS = KD / 16, QROW = row_bytes(KD);
   constexpr int RB = 2 * KMAX * QROW, TB = 2 * D * VST * 2;
   constexpr int CH = D / 4, NE = (KMAX / 2) * CH, NIT = (NE + 255) / 256;
   __shared__ __attribute__((aligned(16))) char lds[2 * RB + TB];
@@ -1610,8 +883,7 @@ window_attn_bwd_q_kernel(const float* __restrict__ qkv, const int* __restrict__ 
   unsigned short* Kt = reinterpret_cast<unsigned short*>(lds + 2 * RB);
 
   const int heads = C / D;
-  const int nb = (int)gridDim.x;
-  const int L = (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8);  // XCD-aware, as the forward
+  const int L = xcd_logical_id();
   if (L >= nwin * heads) return;
   const int w = L / heads, head = L - w * heads;
   const int key_start = win[2 * w], query_start = win[2 * w + 1];
@@ -1621,7 +893,7 @@ window_attn_bwd_q_kernel(const float* __restrict__ qkv, const int* __restrict__ 
   if (tid < KMAX) rows[tid] = tid < Kwin ? order[key_start + tid] : -1;
   if (D < KD)  // zero K / V columns D..KD-1
     for (int rr = tid; rr < 4 * KMAX; rr += 256)
-      *reinterpret_cast<uint4*>(lds + (rr >> 8) * RB + ((rr >> 7) & 1) * KMAX * QROW + bwd_row_off<KD>(rr & 127, D / 8)) =
+      *reinterpret_cast<uint4*>(lds + (rr >> 8) * RB + ((rr >> 7) & 1) * KMAX * QROW + row_off<KD>(rr & 127, D / 8)) =
           make_uint4(0, 0, 0, 0);
   __syncthreads();
   // dqkv is not zero-filled by the caller: the key pass stores every key's dK / dV plainly except the keys a ragged
@@ -1643,10 +915,10 @@ window_attn_bwd_q_kernel(const float* __restrict__ qkv, const int* __restrict__ 
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
     const int d0 = 16 * ks + 8 * h;
-    bwd_load8<D>(qkv + (long long)(qsrc < 0 ? 0 : qsrc) * ld + head * D, d0, qsrc >= 0, qa[ks][0], qa[ks][1]);
-    bwd_load8<D>(dout + (long long)(qsrc < 0 ? 0 : qsrc) * C + head * D, d0, qown, ga[ks][0], ga[ks][1]);
+    load8<D>(qkv + (long long)(qsrc < 0 ? 0 : qsrc) * ld + head * D, d0, qsrc >= 0, qa[ks][0], qa[ks][1]);
+    load8<D>(dout + (long long)(qsrc < 0 ? 0 : qsrc) * C + head * D, d0, qown, ga[ks][0], ga[ks][1]);
     float4 oa, ob;
-    bwd_load8<D>(attn_out + (long long)(qsrc < 0 ? 0 : qsrc) * C + head * D, d0, qown, oa, ob);
+    load8<D>(attn_out + (long long)(qsrc < 0 ? 0 : qsrc) * C + head * D, d0, qown, oa, ob);
     delta += ga[ks][0].x * oa.x + ga[ks][0].y * oa.y + ga[ks][0].z * oa.z + ga[ks][0].w * oa.w +
              ga[ks][1].x * ob.x + ga[ks][1].y * ob.y + ga[ks][1].z * ob.z + ga[ks][1].w * ob.w;
     mx4.x = fmaxf(mx4.x, fmaxf(amax4(qa[ks][0]), amax4(qa[ks][1])));
@@ -1676,23 +948,23 @@ window_attn_bwd_q_kernel(const float* __restrict__ qkv, const int* __restrict__ 
   }
   mx4 = bwd_wg_max4(mx4, red);
   float iQ, iK, iV, iG;
-  const float sQ = bwd_pow2(mx4.x, iQ), sK = bwd_pow2(mx4.y, iK), sV = bwd_pow2(mx4.z, iV),
-              sG = bwd_pow2(mx4.w, iG);
+  const float sQ = sfx::pow2_scale(mx4.x, iQ), sK = sfx::pow2_scale(mx4.y, iK), sV = sfx::pow2_scale(mx4.z, iV),
+              sG = sfx::pow2_scale(mx4.w, iG);
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int e = tid + 256 * it;
     if (e < NE) {
       const int kp = e / CH, ch = e - kp * CH;
-      bwd_stage_pair<D, KD>(Kr, Kt, 2 * kp, ch, k0[it], k1[it], sK);
-      bwd_stage_row<KD>(Vr, 2 * kp, ch, v0[it], sV);
-      bwd_stage_row<KD>(Vr, 2 * kp + 1, ch, v1[it], sV);
+      stage_pair<D, true, KD>(Kr, Kt, 2 * kp, ch, k0[it], k1[it], sK);
+      stage_row<KD, true>(Vr, 2 * kp, ch, v0[it], sV);
+      stage_row<KD, true>(Vr, 2 * kp + 1, ch, v1[it], sV);
     }
   }
   f16x8 qf[NKS][2], gf[NKS][2];
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
-    bwd_frag(qa[ks][0], qa[ks][1], sQ, qf[ks]);
-    bwd_frag(ga[ks][0], ga[ks][1], sG, gf[ks]);
+    frag<true>(qa[ks][0], qa[ks][1], sQ, qf[ks]);
+    frag<true>(ga[ks][0], ga[ks][1], sG, gf[ks]);
   }
   __syncthreads();
 
@@ -1705,8 +977,8 @@ window_attn_bwd_q_kernel(const float* __restrict__ qkv, const int* __restrict__ 
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
       f16x8 kf[2];
-      bwd_row_frag<KD>(Kr, kb * 32 + l32, 2 * ks + h, kf);
-      s[kb] = mfma3<ONE>(kf, qf[ks], s[kb]);
+      row_frag<KD, true>(Kr, kb * 32 + l32, 2 * ks + h, kf);
+      s[kb] = mfma_terms<true, ONE>(kf, qf[ks], s[kb]);
     }
   }
   const float cS = scale * 1.4426950408889634f * iQ * iK;
@@ -1715,22 +987,12 @@ window_attn_bwd_q_kernel(const float* __restrict__ qkv, const int* __restrict__ 
   for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int key = score_key(kb, r, h);
       s[kb][r] = key < Kwin ? s[kb][r] * cS : -INFINITY;
       mx = fmaxf(mx, s[kb][r]);
     }
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float e = __builtin_amdgcn_exp2f(s[kb][r] - mx);
-      s[kb][r] = e;
-      sum += e;
-    }
-  sum += __shfl_xor(sum, 32, 64);
-  const float rinv = 1.f / sum;
+  const float rinv = 1.f / score_exp<true>(s, mx);
   if (h == 0 && qown) stats[(long long)qsrc * heads + head] = make_float4(mx, rinv, delta, 0.f);
 
   // per key block: dP^T = V dO^T, dS^T = P^T (dP^T - Delta), dQ^T += K^T dS^T
@@ -1746,8 +1008,8 @@ window_attn_bwd_q_kernel(const float* __restrict__ qkv, const int* __restrict__ 
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
       f16x8 vf[2];
-      bwd_row_frag<KD>(Vr, kb * 32 + l32, 2 * ks + h, vf);
-      dp = mfma3<ONE>(vf, gf[ks], dp);
+      row_frag<KD, true>(Vr, kb * 32 + l32, 2 * ks + h, vf);
+      dp = mfma_terms<true, ONE>(vf, gf[ks], dp);
     }
     float m = 0.f;
 #pragma unroll
@@ -1757,31 +1019,26 @@ window_attn_bwd_q_kernel(const float* __restrict__ qkv, const int* __restrict__ 
     }
     m = fmaxf(m, __shfl_xor(m, 32, 64));
     float isd;
-    const float sd = bwd_pow2(m, isd);
+    const float sd = sfx::pow2_scale(m, isd);
     floatx16 t;
 #pragma unroll
     for (int r = 0; r < 16; ++r) t[r] = 0.f;
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
       f16x8 bf[2], kt[2];
-      bwd_frag(make_float4(dp[8 * st + 0], dp[8 * st + 1], dp[8 * st + 2], dp[8 * st + 3]),
+      frag<true>(make_float4(dp[8 * st + 0], dp[8 * st + 1], dp[8 * st + 2], dp[8 * st + 3]),
                make_float4(dp[8 * st + 4], dp[8 * st + 5], dp[8 * st + 6], dp[8 * st + 7]), sd, bf);
-      bwd_tr_frag<D>(Kt, l32, 2 * kb + st, h, kt);
-      t = mfma3<ONE>(kt, bf, t);
+      tr_frag<D, true>(Kt, l32, 2 * kb + st, h, kt);
+      t = mfma_terms<true, ONE>(kt, bf, t);
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) dq[r] += t[r] * isd;
   }
   if (qown) {
     const float cQ = scale * iK;
-    float* dst = dqkv + (long long)qsrc * ld + head * D;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int dd = 8 * g + 4 * h;
-      if (dd + 3 < D)
-        *reinterpret_cast<float4*>(dst + dd) =
-            make_float4(dq[4 * g + 0] * cQ, dq[4 * g + 1] * cQ, dq[4 * g + 2] * cQ, dq[4 * g + 3] * cQ);
-    }
+    for (int r = 0; r < 16; ++r) dq[r] *= cQ;
+    store_ot<D>(dqkv + (long long)qsrc * ld + head * D, dq, h);
   }
 }
 
@@ -1790,7 +1047,7 @@ __global__ void __launch_bounds__(256, 3)
 window_attn_bwd_kv_kernel(const float* __restrict__ qkv, const int* __restrict__ order, const int* __restrict__ win,
                           int Kwin, int C, float scale, const float* __restrict__ dout, float* __restrict__ dqkv,
                           const float4* __restrict__ stats, int nwin) {
-  constexpr int KD = D == 16 ? 16 : 32, NKS = KD / 16, QROW = KD == 16 ? 48 : 64, VST = 136;
+  constexpr int KD = D == 16 ? 16 : 32, NKS = KD / 16, QROW = row_bytes(KD);
   constexpr int RB = 2 * KMAX * QROW, TB = 2 * D * VST * 2;
   constexpr int CH = D / 4, NE = (KMAX / 2) * CH, NIT = (NE + 255) / 256;
   constexpr int DP = D + 4;  // fp32 output staging row stride
@@ -1805,8 +1062,7 @@ window_attn_bwd_kv_kernel(const float* __restrict__ qkv, const int* __restrict__
   unsigned short* Gt = reinterpret_cast<unsigned short*>(lds + 2 * RB + TB);
 
   const int heads = C / D;
-  const int nb = (int)gridDim.x;
-  const int L = (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8);
+  const int L = xcd_logical_id();
   if (L >= nwin * heads) return;
   const int w = L / heads, head = L - w * heads;
   const int key_start = win[2 * w], query_start = win[2 * w + 1];
@@ -1823,7 +1079,7 @@ window_attn_bwd_kv_kernel(const float* __restrict__ qkv, const int* __restrict__
   }
   if (D < KD)
     for (int rr = tid; rr < 4 * KMAX; rr += 256)
-      *reinterpret_cast<uint4*>(lds + (rr >> 8) * RB + ((rr >> 7) & 1) * KMAX * QROW + bwd_row_off<KD>(rr & 127, D / 8)) =
+      *reinterpret_cast<uint4*>(lds + (rr >> 8) * RB + ((rr >> 7) & 1) * KMAX * QROW + row_off<KD>(rr & 127, D / 8)) =
           make_uint4(0, 0, 0, 0);
   __syncthreads();
   // this lane's key: k and v slices (B operands of S and dP)
@@ -1836,8 +1092,8 @@ window_attn_bwd_kv_kernel(const float* __restrict__ qkv, const int* __restrict__
   for (int ks = 0; ks < NKS; ++ks) {
     const int d0 = 16 * ks + 8 * h;
     const float* base = qkv + (long long)(key_ok ? ksrc : 0) * ld + head * D;
-    bwd_load8<D>(base + C, d0, key_ok, ka[ks][0], ka[ks][1]);
-    bwd_load8<D>(base + 2 * C, d0, key_ok, va[ks][0], va[ks][1]);
+    load8<D>(base + C, d0, key_ok, ka[ks][0], ka[ks][1]);
+    load8<D>(base + 2 * C, d0, key_ok, va[ks][0], va[ks][1]);
     mx4.y = fmaxf(mx4.y, fmaxf(amax4(ka[ks][0]), amax4(ka[ks][1])));
     mx4.z = fmaxf(mx4.z, fmaxf(amax4(va[ks][0]), amax4(va[ks][1])));
   }
@@ -1865,22 +1121,22 @@ window_attn_bwd_kv_kernel(const float* __restrict__ qkv, const int* __restrict__
   }
   mx4 = bwd_wg_max4(mx4, red);
   float iQ, iK, iV, iG;
-  const float sQ = bwd_pow2(mx4.x, iQ), sK = bwd_pow2(mx4.y, iK), sV = bwd_pow2(mx4.z, iV),
-              sG = bwd_pow2(mx4.w, iG);
+  const float sQ = sfx::pow2_scale(mx4.x, iQ), sK = sfx::pow2_scale(mx4.y, iK), sV = sfx::pow2_scale(mx4.z, iV),
+              sG = sfx::pow2_scale(mx4.w, iG);
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int e = tid + 256 * it;
     if (e < NE) {
       const int qp = e / CH, ch = e - qp * CH;
-      bwd_stage_pair<D, KD>(Qr, Qt, 2 * qp, ch, q0[it], q1[it], sQ);
-      bwd_stage_pair<D, KD>(Gr, Gt, 2 * qp, ch, g0[it], g1[it], sG);
+      stage_pair<D, true, KD>(Qr, Qt, 2 * qp, ch, q0[it], q1[it], sQ);
+      stage_pair<D, true, KD>(Gr, Gt, 2 * qp, ch, g0[it], g1[it], sG);
     }
   }
   f16x8 kf[NKS][2], vf[NKS][2];
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
-    bwd_frag(ka[ks][0], ka[ks][1], sK, kf[ks]);
-    bwd_frag(va[ks][0], va[ks][1], sV, vf[ks]);
+    frag<true>(ka[ks][0], ka[ks][1], sK, kf[ks]);
+    frag<true>(va[ks][0], va[ks][1], sV, vf[ks]);
   }
   __syncthreads();
 
@@ -1896,16 +1152,16 @@ window_attn_bwd_kv_kernel(const float* __restrict__ qkv, const int* __restrict__
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
       f16x8 a[2];
-      bwd_row_frag<KD>(Qr, qb * 32 + l32, 2 * ks + h, a);
-      sb = mfma3<ONE>(a, kf[ks], sb);
-      bwd_row_frag<KD>(Gr, qb * 32 + l32, 2 * ks + h, a);
-      pb = mfma3<ONE>(a, vf[ks], pb);
+      row_frag<KD, true>(Qr, qb * 32 + l32, 2 * ks + h, a);
+      sb = mfma_terms<true, ONE>(a, kf[ks], sb);
+      row_frag<KD, true>(Gr, qb * 32 + l32, 2 * ks + h, a);
+      pb = mfma_terms<true, ONE>(a, vf[ks], pb);
     }
     // rows r: query qb*32 + (r&3) + 8(r>>2) + 4h ; P (<= 1) into sb, dS into pb
     float m = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float4 st = stat[qb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h];
+      const float4 st = stat[score_key(qb, r, h)];
       const float P = key_ok ? __builtin_amdgcn_exp2f(sb[r] * cS - st.x) * st.y : 0.f;
       sb[r] = P;
       pb[r] = P * (pb[r] * cP - st.z);
@@ -1913,21 +1169,21 @@ window_attn_bwd_kv_kernel(const float* __restrict__ qkv, const int* __restrict__
     }
     m = fmaxf(m, __shfl_xor(m, 32, 64));
     float isd;
-    const float sd = bwd_pow2(m, isd);
+    const float sd = sfx::pow2_scale(m, isd);
     floatx16 t;
 #pragma unroll
     for (int r = 0; r < 16; ++r) t[r] = 0.f;
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
       f16x8 bp[2], bd[2], at[2];
-      bwd_frag(make_float4(sb[8 * st + 0], sb[8 * st + 1], sb[8 * st + 2], sb[8 * st + 3]),
+      frag<true>(make_float4(sb[8 * st + 0], sb[8 * st + 1], sb[8 * st + 2], sb[8 * st + 3]),
                make_float4(sb[8 * st + 4], sb[8 * st + 5], sb[8 * st + 6], sb[8 * st + 7]), 16384.f, bp);
-      bwd_tr_frag<D>(Gt, l32, 2 * qb + st, h, at);
-      dv = mfma3<ONE>(at, bp, dv);
-      bwd_frag(make_float4(pb[8 * st + 0], pb[8 * st + 1], pb[8 * st + 2], pb[8 * st + 3]),
+      tr_frag<D, true>(Gt, l32, 2 * qb + st, h, at);
+      dv = mfma_terms<true, ONE>(at, bp, dv);
+      frag<true>(make_float4(pb[8 * st + 0], pb[8 * st + 1], pb[8 * st + 2], pb[8 * st + 3]),
                make_float4(pb[8 * st + 4], pb[8 * st + 5], pb[8 * st + 6], pb[8 * st + 7]), sd, bd);
-      bwd_tr_frag<D>(Qt, l32, 2 * qb + st, h, at);
-      t = mfma3<ONE>(at, bd, t);
+      tr_frag<D, true>(Qt, l32, 2 * qb + st, h, at);
+      t = mfma_terms<true, ONE>(at, bd, t);
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) dk[r] += t[r] * isd;
@@ -1940,7 +1196,7 @@ window_attn_bwd_kv_kernel(const float* __restrict__ qkv, const int* __restrict__
   float* Ov = Ok + KMAX * DP;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int dd = (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int dd = score_key(0, r, h);
     if (dd < D) {
       Ok[kk * DP + dd] = dk[r] * cK;
       Ov[kk * DP + dd] = dv[r] * cV;
@@ -1966,15 +1222,24 @@ window_attn_bwd_kv_kernel(const float* __restrict__ qkv, const int* __restrict__
   }
 }
 
-// SFX_ATTN_SEQ=1: the pipelined kernel (window_attn_seq_kernel) on at most 512 workgroups, SFX_ATTN_SEQ=<n>
-// (n > 1) on at most n; default and 0: one (window, head) item per workgroup (window_attn_split_kernel), which
-// measured faster (config B 568 vs 553 renders/s at 768 / 1024 workgroups, profiles/r04_ab_bench.txt)
-int attn_seq() {
-  const char* e = getenv("SFX_ATTN_SEQ");  // (read per call: tests switch it)
-  if (!e || !e[0]) return 0;
-  const int v = atoi(e);
-  return v == 0 ? 0 : v > 1 ? v : 512;
+// SFX_ATTN_PREC=fp32: the exact v_mfma_f32_32x32x2_f32 kernels (read once per process)
+bool attn_exact() {
+  static int exact = -1;
+  if (exact < 0) {
+    const char* e = getenv("SFX_ATTN_PREC");
+    exact = (e && e[0] == 'f') ? 1 : 0;
+  }
+  return exact != 0;
 }
+// f(head_dim as a compile-time constant); the entry points admit 16, 24 and 32 only
+template <class F>
+void for_head_dim(int head_dim, F&& f) {
+  if (head_dim == 16) f(std::integral_constant<int, 16>{});
+  else if (head_dim == 24) f(std::integral_constant<int, 24>{});
+  else f(std::integral_constant<int, 32>{});
+}
+constexpr std::true_type kTrue{};
+constexpr std::false_type kFalse{};
 
 }  // namespace
 
@@ -1995,49 +1260,22 @@ int sfx_window_attention(int num_windows, int window, int heads, int head_dim, i
   const long long nblk = ((long long)num_windows * heads + 7) / 8 * 8;
   SFX_REQUIRE(nblk < (1ll << 31), "sfx_window_attention: too many windows");
   hipStream_t st = sfx::as_stream(stream);
-  static int exact = -1;  // SFX_ATTN_PREC=fp32: the v_mfma_f32_32x32x2_f32 kernel
-  if (exact < 0) {
-    const char* e = getenv("SFX_ATTN_PREC");
-    exact = (e && e[0] == 'f') ? 1 : 0;
-  }
-  if (exact) {
-    if (head_dim == 16)
-      window_attn_kernel<16><<<grid, 256, 0, st>>>(qkv, order, win, window, channels, scale, out);
-    else if (head_dim == 24)
-      window_attn_kernel<24><<<grid, 256, 0, st>>>(qkv, order, win, window, channels, scale, out);
-    else
-      window_attn_kernel<32><<<grid, 256, 0, st>>>(qkv, order, win, window, channels, scale, out);
-  } else if (const int seq_wgs = qkv_amax ? attn_seq() : 0) {  // fp16x2 terms, pipelined over (window, head) items
-    const int items = num_windows * heads;
-    const int ipw = (items + seq_wgs - 1) / seq_wgs;  // at most seq_wgs workgroups (512: one round at 2 per CU)
-    const long long nwg = ((long long)(items + ipw - 1) / ipw + 7) / 8 * 8;
-#define SFX_ATTN_SEQ(DD)                                                                                     \
-  window_attn_seq_kernel<DD><<<dim3((unsigned)nwg), 256, 0, st>>>(qkv, order, win, window, channels, scale, out, \
-                                                                   qkv_amax, qkv_tag, items, ipw)
-    if (head_dim == 16) SFX_ATTN_SEQ(16);
-    else if (head_dim == 24) SFX_ATTN_SEQ(24);
-    else SFX_ATTN_SEQ(32);
-#undef SFX_ATTN_SEQ
-  } else if (qkv_amax) {  // fp16x2 terms (the caller bounds |qkv|)
-#define SFX_ATTN(DD, F, O)                                                                                  \
-  window_attn_split_kernel<DD, F, O><<<dim3((unsigned)nblk), 256, 0, st>>>(qkv, order, win, window, channels, scale, \
-                                                                           out, qkv_amax, qkv_tag, num_windows)
-    if (sfx_get_precision() == 1) {  // reference-precision mode: single fp16 products
-      if (head_dim == 16) SFX_ATTN(16, true, true);
-      else if (head_dim == 24) SFX_ATTN(24, true, true);
-      else SFX_ATTN(32, true, true);
-    } else if (head_dim == 16) SFX_ATTN(16, true, false);
-    else if (head_dim == 24) SFX_ATTN(24, true, false);
-    else SFX_ATTN(32, true, false);
+  if (attn_exact()) {
+    for_head_dim(head_dim, [&](auto d) {
+      window_attn_kernel<d()><<<grid, 256, 0, st>>>(qkv, order, win, window, channels, scale, out);
+    });
   } else {
-    if (sfx_get_precision() == 1) {
-      if (head_dim == 16) SFX_ATTN(16, false, true);
-      else if (head_dim == 24) SFX_ATTN(24, false, true);
-      else SFX_ATTN(32, false, true);
-    } else if (head_dim == 16) SFX_ATTN(16, false, false);
-    else if (head_dim == 24) SFX_ATTN(24, false, false);
-    else SFX_ATTN(32, false, false);
-#undef SFX_ATTN
+    // fp16x2 terms when the caller bounds |qkv| (amax slot), bf16x3 otherwise; reference-precision mode
+    // (sfx_set_precision(1)): the leading products only
+    const bool one = sfx_get_precision() == 1;
+    for_head_dim(head_dim, [&](auto d) {
+      auto launch = [&](auto f16, auto o) {
+        window_attn_split_kernel<d(), f16(), o()><<<dim3((unsigned)nblk), 256, 0, st>>>(
+            qkv, order, win, window, channels, scale, out, qkv_amax, qkv_tag, num_windows);
+      };
+      if (qkv_amax) { if (one) launch(kTrue, kTrue); else launch(kTrue, kFalse); }
+      else { if (one) launch(kFalse, kTrue); else launch(kFalse, kFalse); }
+    });
   }
   return sfx::check_launch("sfx_window_attention");
 }
@@ -2057,35 +1295,21 @@ int sfx_window_attention_varlen(int num_windows, int max_window, int heads, int 
   const long long nblk = ((long long)num_windows * qblocks * heads + 7) / 8 * 8;
   SFX_REQUIRE(nblk < (1ll << 31) && heads <= 65535, "sfx_window_attention_varlen: grid too large");
   hipStream_t st = sfx::as_stream(stream);
-  static int exact = -1;  // SFX_ATTN_PREC=fp32: the v_mfma_f32_32x32x2_f32 kernel
-  if (exact < 0) {
-    const char* e = getenv("SFX_ATTN_PREC");
-    exact = (e && e[0] == 'f') ? 1 : 0;
-  }
-  if (exact) {
+  if (attn_exact()) {
     dim3 grid((unsigned)(num_windows * qblocks), heads);
-    if (head_dim == 16)
-      window_attn_flash_kernel<16><<<grid, 256, 0, st>>>(qkv, order, win3, qblocks, channels, scale, out);
-    else if (head_dim == 24)
-      window_attn_flash_kernel<24><<<grid, 256, 0, st>>>(qkv, order, win3, qblocks, channels, scale, out);
-    else
-      window_attn_flash_kernel<32><<<grid, 256, 0, st>>>(qkv, order, win3, qblocks, channels, scale, out);
+    for_head_dim(head_dim, [&](auto d) {
+      window_attn_flash_kernel<d()><<<grid, 256, 0, st>>>(qkv, order, win3, qblocks, channels, scale, out);
+    });
     return sfx::check_launch("sfx_window_attention_varlen");
   }
-#define SFX_ATTN(DD, F)                                                                                       \
-  window_attn_split_flash_kernel<DD, F><<<dim3((unsigned)nblk), 256, 0, st>>>(qkv, order, win3, qblocks, channels, \
-                                                                              scale, out, qkv_amax, qkv_tag,   \
-                                                                              num_windows)
-  if (qkv_amax) {  // fp16x2 terms (the caller bounds |qkv|)
-    if (head_dim == 16) SFX_ATTN(16, true);
-    else if (head_dim == 24) SFX_ATTN(24, true);
-    else SFX_ATTN(32, true);
-  } else {
-    if (head_dim == 16) SFX_ATTN(16, false);
-    else if (head_dim == 24) SFX_ATTN(24, false);
-    else SFX_ATTN(32, false);
-  }
-#undef SFX_ATTN
+  for_head_dim(head_dim, [&](auto d) {
+    auto launch = [&](auto f16) {
+      window_attn_split_flash_kernel<d(), f16()><<<dim3((unsigned)nblk), 256, 0, st>>>(
+          qkv, order, win3, qblocks, channels, scale, out, qkv_amax, qkv_tag, num_windows);
+    };
+    if (qkv_amax) launch(kTrue);  // fp16x2 terms (the caller bounds |qkv|)
+    else launch(kFalse);
+  });
   return sfx::check_launch("sfx_window_attention_varlen");
 }
 
@@ -2106,17 +1330,11 @@ int sfx_window_attention_varlen_bwd(int num_windows, int max_window, int heads, 
               "sfx_window_attention_varlen_bwd: grid too large");
   dim3 grid((unsigned)(num_windows * blocks), heads);
   hipStream_t st = sfx::as_stream(stream);
-#define SFX_FBWD(DD)                                                                                           \
-  do {                                                                                                         \
-    flash_bwd_query_kernel<DD><<<grid, FB, 0, st>>>(qkv, order, win3, blocks, channels, heads, scale, dout, dqkv, \
-                                                     stats);                                                   \
-    flash_bwd_key_kernel<DD><<<grid, FB, 0, st>>>(qkv, order, win3, blocks, channels, heads, scale, dout, dqkv, \
-                                                   stats);                                                     \
-  } while (0)
-  if (head_dim == 16) SFX_FBWD(16);
-  else if (head_dim == 24) SFX_FBWD(24);
-  else SFX_FBWD(32);
-#undef SFX_FBWD
+  for_head_dim(head_dim, [&](auto d) {
+    flash_bwd_query_kernel<d()><<<grid, FB, 0, st>>>(qkv, order, win3, blocks, channels, heads, scale, dout, dqkv,
+                                                      stats);
+    flash_bwd_key_kernel<d()><<<grid, FB, 0, st>>>(qkv, order, win3, blocks, channels, heads, scale, dout, dqkv, stats);
+  });
   return sfx::check_launch("sfx_window_attention_varlen_bwd");
 }
 
@@ -2134,38 +1352,28 @@ int sfx_window_attention_bwd(int num_windows, int window, int heads, int head_di
   if (num_windows == 0) return SFX_OK;
   SFX_REQUIRE(qkv && order && win && dout && dqkv, "sfx_window_attention_bwd: null buffer");
   hipStream_t st = sfx::as_stream(stream);
-  static int exact = -1;
-  if (exact < 0) {
-    const char* e = getenv("SFX_ATTN_PREC");
-    exact = (e && e[0] == 'f') ? 1 : 0;
-  }
-  if (!exact) {
+  if (!attn_exact()) {
     SFX_REQUIRE(attn_out && stats, "sfx_window_attention_bwd: null attn_out / stats");
     const long long nblk = ((long long)num_windows * heads + 7) / 8 * 8;
     SFX_REQUIRE(nblk < (1ll << 31), "sfx_window_attention_bwd: too many windows");
     float4* st4 = reinterpret_cast<float4*>(stats);
-#define SFX_ABWD(DD, ONE)                                                                                         \
-  do {                                                                                                            \
-    window_attn_bwd_q_kernel<DD, ONE><<<dim3((unsigned)nblk), 256, 0, st>>>(qkv, order, win, window, channels,    \
-                                                                            scale, attn_out, dout, dqkv, st4,    \
-                                                                            num_windows);                         \
-    window_attn_bwd_kv_kernel<DD, ONE><<<dim3((unsigned)nblk), 256, 0, st>>>(qkv, order, win, window, channels,   \
-                                                                             scale, dout, dqkv, st4, num_windows); \
-  } while (0)
     const bool one = sfx_get_precision() == 1;  // reference-precision mode: single fp16 products
-    if (head_dim == 16) { if (one) SFX_ABWD(16, true); else SFX_ABWD(16, false); }
-    else if (head_dim == 24) { if (one) SFX_ABWD(24, true); else SFX_ABWD(24, false); }
-    else { if (one) SFX_ABWD(32, true); else SFX_ABWD(32, false); }
-#undef SFX_ABWD
+    for_head_dim(head_dim, [&](auto d) {
+      auto launch = [&](auto o) {
+        window_attn_bwd_q_kernel<d(), o()><<<dim3((unsigned)nblk), 256, 0, st>>>(
+            qkv, order, win, window, channels, scale, attn_out, dout, dqkv, st4, num_windows);
+        window_attn_bwd_kv_kernel<d(), o()><<<dim3((unsigned)nblk), 256, 0, st>>>(
+            qkv, order, win, window, channels, scale, dout, dqkv, st4, num_windows);
+      };
+      if (one) launch(kTrue);
+      else launch(kFalse);
+    });
     return sfx::check_launch("sfx_window_attention_bwd");
   }
   dim3 grid(num_windows, heads);
-  if (head_dim == 16)
-    window_attn_bwd_kernel<16><<<grid, 256, 0, st>>>(qkv, order, win, window, channels, scale, dout, dqkv);
-  else if (head_dim == 24)
-    window_attn_bwd_kernel<24><<<grid, 256, 0, st>>>(qkv, order, win, window, channels, scale, dout, dqkv);
-  else
-    window_attn_bwd_kernel<32><<<grid, 256, 0, st>>>(qkv, order, win, window, channels, scale, dout, dqkv);
+  for_head_dim(head_dim, [&](auto d) {
+    window_attn_bwd_kernel<d()><<<grid, 256, 0, st>>>(qkv, order, win, window, channels, scale, dout, dqkv);
+  });
   return sfx::check_launch("sfx_window_attention_bwd");
 }
 

@@ -27,22 +27,11 @@
 // kernel's argument), so the refine keeps its 1e-5 bar.
 #include <cstdlib>
 
-#include "common.h"
+#include "attn_common.h"
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-
-constexpr int KMAX = 128;
-
-// V^T chunk swizzle (attention.hip vt_swz): chunk c of V^T row dd at c ^ 2 parity(dd >> 2)
-__device__ __forceinline__ int vt_swz(int dd) { return (__builtin_popcount((unsigned)(dd >> 2)) & 1) << 1; }
-
-__device__ __forceinline__ floatx16 mfma16(const f16x8& a, const f16x8& b, floatx16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
+using namespace sfxa;
 
 // LDS-DMA piece: 16 B per lane from its own global address to M0 + 16 lane (inline asm, as subm_fused.hip: the
 // builtin makes the compiler drain vmcnt whenever an address register is reused; here every wait is ours)
@@ -67,7 +56,6 @@ attn_proj_kernel(const float* __restrict__ qkv, const int* __restrict__ order, c
   constexpr int H = C / D;
   constexpr int NKS = (D + 15) / 16;  // 16-deep k-steps over a head's dd (S^T contraction and projection)
   constexpr int CH = D / 4;           // 16-byte pieces per head row slice (fp32 q / k / v, pre-split Wp groups)
-  constexpr int VST = 136;            // V^T row stride (16-bit elements)
   constexpr int VB = 2 * D * VST * 2;
   constexpr int KRAW = KMAX * CH * 16, WRAW = C * CH * 16;
   constexpr int RAW = 2 * KRAW + WRAW;  // one head's raw K, V and Wp slices
@@ -79,26 +67,15 @@ attn_proj_kernel(const float* __restrict__ qkv, const int* __restrict__ order, c
   constexpr int KPIECES = KMAX * CH / 64, WPIECES = C * CH / 64;  // DMA instructions per slice
   static_assert(C % 32 == 0 && C % D == 0 && (KMAX * CH) % 64 == 0 && (C * CH) % 64 == 0, "shape");
 
-  float sq = 1.f, iq = 1.f;
-  {
-    const float m = sfx::read_amax(qkv_amax, qkv_tag);
-    int e = 0;
-    if (m > 0.f && m <= 3.4028235e38f) {
-      (void)frexpf(m, &e);
-      e = 15 - e;
-      e = e > 126 ? 126 : (e < -126 ? -126 : e);
-    }
-    sq = ldexpf(1.f, e);
-    iq = ldexpf(1.f, -e);
-  }
+  float iq;
+  const float sq = sfx::pow2_scale(sfx::read_amax(qkv_amax, qkv_tag), iq);
 
   __shared__ __attribute__((aligned(16))) char lds[NBUF * RAW + VB];
   __shared__ int rows[KMAX];
   unsigned short* Vt = reinterpret_cast<unsigned short*>(lds + NBUF * RAW);
   const unsigned lds_base = (unsigned)(uintptr_t)lds;
 
-  const int nb = (int)gridDim.x;
-  const int L = (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8);
+  const int L = xcd_logical_id();
   if (L >= nwin * QS) return;
   const int w = L / QS, qh = L - w * QS;
   const int key_start = win[2 * w], query_start = win[2 * w + 1];
@@ -139,16 +116,8 @@ attn_proj_kernel(const float* __restrict__ qkv, const int* __restrict__ order, c
   float4 qa[NKS], qb[NKS];
   auto load_q = [&](int hd) {
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const int d0 = 16 * ks + 8 * h;
-      qa[ks] = make_float4(0.f, 0.f, 0.f, 0.f);
-      qb[ks] = qa[ks];
-      if (qrow >= 0 && d0 < D) {
-        const float* qp = qkv + (long long)qrow * ld + hd * D + d0;
-        qa[ks] = *reinterpret_cast<const float4*>(qp);
-        if (d0 + 4 < D) qb[ks] = *reinterpret_cast<const float4*>(qp + 4);
-      }
-    }
+    for (int ks = 0; ks < NKS; ++ks)
+      load8<D>(qkv + (long long)max(qrow, 0) * ld + hd * D, 16 * ks + 8 * h, qrow >= 0, qa[ks], qb[ks]);
   };
 
   floatx16 y[NCB];
@@ -169,16 +138,7 @@ attn_proj_kernel(const float* __restrict__ qkv, const int* __restrict__ order, c
     // q fragments of this head (loaded one head ahead)
     f16x8 qf[NKS][2];
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      float4 a = qa[ks], b = qb[ks];
-      a.x *= qs; a.y *= qs; a.z *= qs; a.w *= qs;
-      b.x *= qs; b.y *= qs; b.z *= qs; b.w *= qs;
-      uint2 ta[2], tb[2];
-      sfx::split2h(a, sq, ta);  // (|q * qs| <= |q|: the qkv bound holds)
-      sfx::split2h(b, sq, tb);
-#pragma unroll
-      for (int q = 0; q < 2; ++q) qf[ks][q] = __builtin_bit_cast(f16x8, (uintx4){ta[q].x, ta[q].y, tb[q].x, tb[q].y});
-    }
+    for (int ks = 0; ks < NKS; ++ks) q_frag<true>(qa[ks], qb[ks], qs, sq, qf[ks]);
     if (NBUF == 2 && hd + 1 < H) {  // the next head's slices fly while this one computes
       issue(hd + 1, buf ^ 1);
       load_q(hd + 1);
@@ -189,19 +149,7 @@ attn_proj_kernel(const float* __restrict__ qkv, const int* __restrict__ order, c
       const int row = 2 * kp;
       const float4 v0 = *reinterpret_cast<const float4*>(raw + KRAW + 16 * raw_slot<CH>(row, ch));
       const float4 v1 = *reinterpret_cast<const float4*>(raw + KRAW + 16 * raw_slot<CH>(row + 1, ch));
-      uint2 t0[2], t1[2];
-      sfx::split2h(v0, sq, t0);
-      sfx::split2h(v1, sq, t1);
-      const int kk = row & 15;  // even: keys row, row + 1 land on adjacent positions
-      const int pos = (row & ~15) + 8 * ((kk >> 2) & 1) + (((kk >> 3) << 2) | (kk & 3));
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        unsigned* vt = reinterpret_cast<unsigned*>(Vt + (q * D + 4 * ch) * VST + (pos ^ (8 * vt_swz(4 * ch))));
-        vt[0] = (t0[q].x & 0xffffu) | (t1[q].x << 16);
-        vt[VST / 2] = (t0[q].x >> 16) | (t1[q].x & 0xffff0000u);
-        vt[VST] = (t0[q].y & 0xffffu) | (t1[q].y << 16);
-        vt[3 * VST / 2] = (t0[q].y >> 16) | (t1[q].y & 0xffff0000u);
-      }
+      stage_pair<D, true>(nullptr, Vt, row, ch, v0, v1, sq);
     }
     __syncthreads();  // V^T written
 
@@ -230,14 +178,9 @@ attn_proj_kernel(const float* __restrict__ qkv, const int* __restrict__ order, c
             a = *reinterpret_cast<const float4*>(raw + 16 * raw_slot<CH>(kb * 32 + l32, p0));
             b = *reinterpret_cast<const float4*>(raw + 16 * raw_slot<CH>(kb * 32 + l32, p0 + 1));
           }
-          uint2 ta[2], tb[2];
-          sfx::split2h(a, sq, ta);
-          sfx::split2h(b, sq, tb);
-          const f16x8 kh = __builtin_bit_cast(f16x8, (uintx4){ta[0].x, ta[0].y, tb[0].x, tb[0].y});
-          const f16x8 kl = __builtin_bit_cast(f16x8, (uintx4){ta[1].x, ta[1].y, tb[1].x, tb[1].y});
-          s[j] = mfma16(kl, qf[ks][0], s[j]);
-          s[j] = mfma16(kh, qf[ks][1], s[j]);
-          s[j] = mfma16(kh, qf[ks][0], s[j]);
+          f16x8 kf[2];
+          frag<true>(a, b, sq, kf);
+          s[j] = mfma_terms<true>(kf, qf[ks], s[j]);
         }
       float pm = -INFINITY;
 #pragma unroll
@@ -274,21 +217,19 @@ attn_proj_kernel(const float* __restrict__ qkv, const int* __restrict__ order, c
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
           const int kb = ps * KBP + j;
-          uint2 a[2], b[2];
-          sfx::split2h(make_float4(s[j][8 * st + 0], s[j][8 * st + 1], s[j][8 * st + 2], s[j][8 * st + 3]), 16384.f, a);
-          sfx::split2h(make_float4(s[j][8 * st + 4], s[j][8 * st + 5], s[j][8 * st + 6], s[j][8 * st + 7]), 16384.f, b);
-          const f16x8 ph = __builtin_bit_cast(f16x8, make_uint4(a[0].x, a[0].y, b[0].x, b[0].y));
-          const f16x8 pl = __builtin_bit_cast(f16x8, make_uint4(a[1].x, a[1].y, b[1].x, b[1].y));
+          f16x8 pf[2];
+          frag<true>(make_float4(s[j][8 * st + 0], s[j][8 * st + 1], s[j][8 * st + 2], s[j][8 * st + 3]),
+                     make_float4(s[j][8 * st + 4], s[j][8 * st + 5], s[j][8 * st + 6], s[j][8 * st + 7]), 16384.f, pf);
+          // (the V^T fragment read stays written out: tr_frag's (q D + l32) VST address form reschedules 10-25 % of
+          // this kernel's instructions)
           uint4 vh = make_uint4(0, 0, 0, 0), vl = vh;  // dd = l32 >= D: zero rows of V^T
           if (l32 < D) {
             const int co = ((2 * (2 * kb + st) + h) ^ vt_swz(l32)) << 3;
             vh = *reinterpret_cast<const uint4*>(Vt + l32 * VST + co);
             vl = *reinterpret_cast<const uint4*>(Vt + (D + l32) * VST + co);
           }
-          const f16x8 fvh = __builtin_bit_cast(f16x8, vh), fvl = __builtin_bit_cast(f16x8, vl);
-          o = mfma16(fvl, ph, o);
-          o = mfma16(fvh, pl, o);
-          o = mfma16(fvh, ph, o);
+          const f16x8 vf[2] = {__builtin_bit_cast(f16x8, vh), __builtin_bit_cast(f16x8, vl)};
+          o = mfma_terms<true>(vf, pf, o);
         }
     }
     const float rinv = 1.f / sum;
@@ -298,22 +239,18 @@ attn_proj_kernel(const float* __restrict__ qkv, const int* __restrict__ order, c
     const float osc = rinv * (1.f / 16384.f);  // o = 2^14 sq sum_k p v  ->  O sq
 #pragma unroll
     for (int sp = 0; sp < NKS; ++sp) {
-      uint2 a[2], b[2];
-      sfx::split2h(make_float4(o[8 * sp + 0], o[8 * sp + 1], o[8 * sp + 2], o[8 * sp + 3]), osc, a);
-      sfx::split2h(make_float4(o[8 * sp + 4], o[8 * sp + 5], o[8 * sp + 6], o[8 * sp + 7]), osc, b);
-      const f16x8 oh = __builtin_bit_cast(f16x8, make_uint4(a[0].x, a[0].y, b[0].x, b[0].y));
-      const f16x8 ol = __builtin_bit_cast(f16x8, make_uint4(a[1].x, a[1].y, b[1].x, b[1].y));
+      f16x8 of[2];
+      frag<true>(make_float4(o[8 * sp + 0], o[8 * sp + 1], o[8 * sp + 2], o[8 * sp + 3]),
+                 make_float4(o[8 * sp + 4], o[8 * sp + 5], o[8 * sp + 6], o[8 * sp + 7]), osc, of);
       const int g0 = 4 * sp + h, g1 = g0 + 2;
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
         uint4 wa = make_uint4(0, 0, 0, 0), wb = wa;
         if (4 * g0 < D) wa = *reinterpret_cast<const uint4*>(raw + 2 * KRAW + 16 * raw_slot<CH>(cb * 32 + l32, g0));
         if (4 * g1 < D) wb = *reinterpret_cast<const uint4*>(raw + 2 * KRAW + 16 * raw_slot<CH>(cb * 32 + l32, g1));
-        const f16x8 wh = __builtin_bit_cast(f16x8, make_uint4(wa.x, wa.y, wb.x, wb.y));
-        const f16x8 wl = __builtin_bit_cast(f16x8, make_uint4(wa.z, wa.w, wb.z, wb.w));
-        y[cb] = mfma16(wl, oh, y[cb]);
-        y[cb] = mfma16(wh, ol, y[cb]);
-        y[cb] = mfma16(wh, oh, y[cb]);
+        const f16x8 wf[2] = {__builtin_bit_cast(f16x8, make_uint4(wa.x, wa.y, wb.x, wb.y)),   // h
+                             __builtin_bit_cast(f16x8, make_uint4(wa.z, wa.w, wb.z, wb.w))};  // l
+        y[cb] = mfma_terms<true>(wf, of, y[cb]);
       }
     }
     if (hd + 1 < H) {

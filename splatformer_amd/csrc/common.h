@@ -81,6 +81,17 @@ __device__ __forceinline__ void split2h(float4 v, float s, uint2 (&t)[2]) {
   const sfx_f16x2 h0 = __builtin_bit_cast(sfx_f16x2, u0), h1 = __builtin_bit_cast(sfx_f16x2, u1);
   t[1] = make_uint2(pk_f16(x0 - (float)h0.x, x1 - (float)h0.y), pk_f16(x2 - (float)h1.x, x3 - (float)h1.y));
 }
+// split2h's operand scale: the power of two s with m * s in [2^14, 2^15) (1 for m == 0 or non-finite m); inv = 1 / s
+__device__ __forceinline__ float pow2_scale(float m, float& inv) {
+  int e = 0;
+  if (m > 0.f && m <= 3.4028235e38f) {
+    (void)frexpf(m, &e);
+    e = 15 - e;
+    e = e > 126 ? 126 : (e < -126 ? -126 : e);
+  }
+  inv = ldexpf(1.f, -e);
+  return ldexpf(1.f, e);
+}
 
 // amax slots (fp16x2 GEMM operand scales): 64 u64 sub-slots holding (tag << 32 | bits of a non-negative float),
 // written with atomicMax (larger tags supersede older contents), read as the max over the sub-slots that carry

@@ -349,13 +349,8 @@ __global__ void __launch_bounds__(256) cpe_ln_qkv_kernel(int M, const float* __r
 #pragma unroll
     for (int i = 0; i < NV; ++i) m = fmaxf(m, fmaxf(fmaxf(fabsf(o[i].x), fabsf(o[i].y)), fmaxf(fabsf(o[i].z), fabsf(o[i].w))));
     m = group_max<G>(m);
-    int e = 0;
-    if (m > 0.f && m <= 3.4028235e38f) {
-      (void)frexpf(m, &e);
-      e = 15 - e;
-      e = e > 126 ? 126 : (e < -126 ? -126 : e);
-    }
-    const float sc = ldexpf(1.f, e);
+    float isc;
+    const float sc = sfx::pow2_scale(m, isc);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c0 = 4 * (sub + G * i);  // channels c0 .. c0 + 3: half (c0 & 4) of 16-byte chunk c0 / 8
@@ -365,7 +360,7 @@ __global__ void __launch_bounds__(256) cpe_ln_qkv_kernel(int M, const float* __r
       *reinterpret_cast<uint2*>(H0 + off) = t[0];
       *reinterpret_cast<uint2*>(H1 + off) = t[1];
     }
-    if (sub == 0) rsc[wid][lr] = ldexpf(1.f, -e);
+    if (sub == 0) rsc[wid][lr] = isc;
   }
   __syncthreads();
 
