@@ -650,6 +650,32 @@ size_t sfx_image_loss_workspace_bytes(int num_images, int height, int width, int
 int sfx_image_loss(int num_images, int height, int width, int channels, const float* pred, const float* gt,
                    const float* window, float l1_weight, float ssim_weight, const float* view_scale, float* terms,
                    float* d_pred, void* ws, size_t ws_bytes, void* stream);
+/* (ABI v16, additive) Fused evaluation metrics of RGB predictions against RGB or masked RGBA targets: the uint8
+ * quantisation, the object mask of a 'real' scene (train.py:104-113, branch gt_imgs.shape[-1] == 4), the integer
+ * moments of sfx_image_stats_u8 and the SSIM of sfx_ssim(quantize_u8 = 1), in one pass over pred and gt.
+ * pred: [num_images][height][width][3] fp32.  gt: [num_images][height][width][gt_pixel_stride] fp32, stride 3 or
+ * 4; only its first three channels are the target.  mask: NULL (none), or one fp32 per pixel, mask_pixel_stride
+ * floats apart: 4 with mask = gt + 3 is the 4th channel of an RGBA target read in place (one 16-byte load per
+ * pixel when gt is 16-byte aligned), 1 is a dense [num_images][height][width] plane.
+ * Per pixel and channel, in the reference's order: p = pred (fminf(p, 1) when clamp_pred != 0); with a mask
+ * p = p * m, one fp32 multiply; qp = (int)(p * 255.f), a second one, truncated and saturated to [0, 255];
+ * qg = (int)(g * 255.f) -- the target is NOT multiplied by the mask.
+ * sums[img*3 + {0,1,2}] = exact sum(qp^2), sum(qg^2), sum(qp*qg) over the 3*height*width values;
+ * maxes[img*2 + {0,1}] = max(qp), max(qg) (the metrics.py:26-29 rule is the host's); both are zeroed by the call.
+ * ssim[img] = utils/metrics.py:93-135 of qp / 255.f and qg / 255.f (window 11, sigma 1.5, zero padding, mean over
+ * the 3 channels and all pixels, no mask weighting).  window: the 11 fp32 taps of the normalised 1-D Gaussian, as
+ * sfx_image_loss; applied separably with fp64 sums.  Every floating-point sum has one fixed order (per-tile
+ * partials, then a fixed-order reduce; integer atomics only): the same inputs give the same bits.
+ * ws: 8-byte aligned, sfx_eval_metrics_workspace_bytes (one double per 32 x 16 tile and image; 0 for sizes the
+ * call refuses).  num_images == 0 returns SFX_OK.
+ * Refused (rc < 0, no launch): sizes < 1, more than 65535 images or 2^40 pixels, height above 16 * 65535,
+ * gt_pixel_stride not 3 or 4, mask_pixel_stride not 1 or 4 with a mask, a null buffer, a short or misaligned
+ * workspace. */
+size_t sfx_eval_metrics_workspace_bytes(int num_images, int height, int width);
+int sfx_eval_metrics_u8(int num_images, int height, int width, const float* pred, const float* gt,
+                        int gt_pixel_stride, const float* mask, int mask_pixel_stride, int clamp_pred,
+                        const float* window, unsigned long long* sums, int* maxes, float* ssim, void* ws,
+                        size_t ws_bytes, void* stream);
 
 /* Point-cloud downsampling experiments (reference models/pcd_downsampling_methods.py; FeaturePredictor
  * additional_info["downsample"], models/feature_predictor.py:159-196).

@@ -5,45 +5,93 @@ per forward, feature_predictor.py:244), render the V test views of the refined G
 (gs_utils.rasterize_gaussians_to_multiimgs), quantise prediction and target to uint8 and accumulate the
 per-image PSNR and SSIM sums (train.py:104-131, utils/metrics.py); finally reduce to rank 0
 (train.py:170-176).  LPIPS (VGG weights, unavailable offline) is out of scope.
+
+Masked branch (train.py:104-109, 'real' scenes): a target with a fourth channel (dataset/GS.py:128-151, the
+object mask appended by scene_io.read_image) takes `pred = pred * mask` before the uint8 truncation; the target
+is used as composited and the metrics run over all pixels.  That branch is one fused kernel
+(metrics.eval_metrics_u8) reading the RGBA target in place; 3-channel targets keep the two kernels they had.
+The per-scene, per-image record (MetricComputer.results_dict, utils/metrics.py:48, written as
+metrics.rank{r}.json by :82-84 / train.py:165) and `compare_with_input` (train.py:127-136, :184-189) are
+optional outputs of the same loop.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, Sequence
+import json
+from typing import Callable, Dict, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib, dist
 from .gs_render import rasterize_gaussians_to_multiimgs
-from .metrics import image_stats_u8, psnr_from_stats, ssim
+from .metrics import eval_metrics_u8, image_stats_u8, psnr_from_stats, ssim
+
+
+def _score(pred: torch.Tensor, gt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-image (psnr, ssim), float64 on the host, of rendered `pred` [V,H,W,3] against gt [V,H,W,3 or 4]."""
+    if gt.shape[-1] == 4:  # train.py:104-109: mask the prediction, one fused pass over the RGBA target
+        m = eval_metrics_u8(pred, gt, clamp_pred=False)  # rgbs are already clamped (gs_utils.py:111)
+        return m["psnr"], m["ssim"].double().cpu()
+    sums, maxes = image_stats_u8(pred, gt, clamp_pred=False)  # rgbs are already clamped (gs_utils.py:111)
+    psnr = psnr_from_stats(sums, maxes, pred[0].numel())
+    return psnr, ssim(pred, gt, quantize_u8=True).double().cpu()
+
+
+def _record(results: Optional[dict], name: str, psnr: torch.Tensor, ssim_: torch.Tensor) -> None:
+    if results is not None:
+        results[name] = {"psnr": psnr.tolist(), "ssim": ssim_.tolist()}
 
 
 @torch.no_grad()
 def evaluate_scenes(model, scenes: Sequence[dict], cameras: Sequence[dict],
                     targets: Callable[[int], torch.Tensor], device: torch.device,
-                    evaluate_input: bool = False) -> Dict[str, float]:
+                    evaluate_input: bool = False, *, results: Optional[dict] = None,
+                    names: Optional[Sequence[str]] = None, compare_with_input: bool = False,
+                    results_input: Optional[dict] = None) -> Dict[str, float]:
     """Evaluate this rank's chunk of `scenes`.
 
     scenes[i]: normalized Gaussian dict (device tensors); cameras[i]: camera dict (device tensors);
-    targets(i): [V,H,W,3] ground-truth images in [0,1] for scene i (device).
+    targets(i): [V,H,W,3] ground-truth images in [0,1] for scene i (device), or [V,H,W,4] for a 'real' scene: the
+    composited RGB plus the object mask (scene_io.read_image), scored through the mask.  A chunk may mix the two.
+    results: a dict filled in place with this rank's record, results[name][metric] = [one float per image], metric
+    in ("psnr", "ssim") -- the reference's MetricComputer.results_dict; name is str(i), or names[i] when `names`
+    is given.  write_metrics() writes it as the reference's metrics.rank{r}.json.
+    compare_with_input: also render scenes[i] itself and score it against the same targets and mask
+    (train.py:127-136); the return value gains "psnr_input" and "ssim_input", reduced like the others.  Its
+    per-image record goes to a second dict, `results_input` (same layout; the reference's
+    metrics_input.rank{r}.json), not under a key of `results`.
     Returns the rank-0 reduced means ({} on other ranks)."""
     rank, ws = dist.world()
     mine = dist.scene_chunk(len(scenes), rank, ws)
-    psnr_sum = torch.zeros((), dtype=torch.float64)
-    ssim_sum = torch.zeros((), dtype=torch.float64)
+    keys = ("psnr", "ssim") + (("psnr_input", "ssim_input") if compare_with_input else ())
+    total = {k: torch.zeros((), dtype=torch.float64) for k in keys}
     num_images = 0
     for i in mine:
         gs = scenes[i] if evaluate_input else model([scenes[i]], [i])[0]
         rgbs, _ = rasterize_gaussians_to_multiimgs(gs, cameras[i])
         pred = torch.stack(rgbs, 0)
         gt = targets(i)
-        sums, maxes = image_stats_u8(pred, gt, clamp_pred=False)  # rgbs are already clamped (gs_utils.py:111)
-        psnr = psnr_from_stats(sums, maxes, pred[0].numel())
-        psnr_sum += psnr.sum()
-        ssim_sum += ssim(pred, gt, quantize_u8=True).double().sum().cpu()
+        name = str(i) if names is None else names[i]
+        psnr, ssim_ = _score(pred, gt)
+        total["psnr"] += psnr.sum()
+        total["ssim"] += ssim_.sum()
+        _record(results, name, psnr, ssim_)
+        if compare_with_input:
+            if not evaluate_input:  # otherwise the prediction IS the input's render
+                rgbs, _ = rasterize_gaussians_to_multiimgs(scenes[i], cameras[i])
+                psnr, ssim_ = _score(torch.stack(rgbs, 0), gt)
+            total["psnr_input"] += psnr.sum()
+            total["ssim_input"] += ssim_.sum()
+            _record(results_input, name, psnr, ssim_)
         num_images += pred.shape[0]
         if not evaluate_input and hasattr(model, "check_refine"):
             model.check_refine()  # the refine's deferred pooling checks, at the readback that consumes it
         else:
             _lib.check_lookback("evaluate_scenes")  # the render's intersection scans / sorts
-    return dist.reduce_metrics({"psnr": psnr_sum, "ssim": ssim_sum}, num_images, len(mine),
+    return dist.reduce_metrics(total, num_images, len(mine),
                                device=device if ws > 1 and device.type == "cuda" else None)
+
+
+def write_metrics(results: dict, path: str) -> None:
+    """MetricComputer.write_to_file (utils/metrics.py:82-84): the per-scene, per-image record as JSON."""
+    with open(path, "w") as f:
+        json.dump(results, f, indent=4)

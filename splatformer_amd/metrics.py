@@ -11,6 +11,10 @@ The quantisation and the per-image integer moments run in one HIP kernel (sfx_im
 formed on the host from the exact integer sums.  Divergence (documented): when a batch's max is <= 1 and
 the OTHER batch's is too, the reference subtracts two uint8 tensors (wrap-around) and then fails in
 `.mean()` on a Byte tensor; here the values are used unscaled instead.
+
+`eval_metrics_u8(pred, gt, mask)` is the same contract with the object mask of a 'real' scene (train.py:104-109:
+the prediction alone is multiplied by the mask before the truncation) and the SSIM of the same uint8 images, from
+one fused kernel (sfx_eval_metrics_u8) that reads an RGBA target in place.
 """
 from __future__ import annotations
 
@@ -94,3 +98,60 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor, quantize_u8: bool = False) -> t
          stream())
     return out
 
+
+_TAPS = {}
+
+
+def eval_stats_u8(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor | None = None,
+                  clamp_pred: bool = True):
+    """The launch of eval_metrics_u8 alone, nothing read back: (sums [V,3] int64, maxes [V,2] int32, ssim [V]
+    float32), all on the device.  Shapes as eval_metrics_u8."""
+    if pred.dim() != 4 or pred.shape[-1] != 3:
+        raise ValueError(f"eval_metrics_u8: pred must be [V,H,W,3], got {tuple(pred.shape)}")
+    if gt.dim() != 4 or gt.shape[-1] not in (3, 4) or gt.shape[:3] != pred.shape[:3]:
+        raise ValueError(f"eval_metrics_u8: gt must be [V,H,W,3] or [V,H,W,4] over pred's {tuple(pred.shape[:3])} "
+                         f"pixels, got {tuple(gt.shape)}")
+    V, H, W, _ = pred.shape
+    if mask is not None and tuple(mask.shape) not in ((V, H, W), (V, H, W, 1)):
+        raise ValueError(f"eval_metrics_u8: mask must be [V,H,W] or [V,H,W,1] over pred's pixels, "
+                         f"got {tuple(mask.shape)}")
+    _lib.require_gpu(pred)
+    pred = pred.float().contiguous()
+    gt = gt.float().contiguous()
+    gs = gt.shape[-1]
+    if mask is not None:
+        mask = mask.float().contiguous()
+        mptr, ms = ptr(mask), 1
+    elif gs == 4:
+        mptr, ms = ptr(gt) + 3 * gt.element_size(), 4  # the 4th channel, where it lies
+    else:
+        mptr, ms = None, 0
+    dev = pred.device
+    taps = _TAPS.get(dev)
+    if taps is None:
+        taps = _TAPS[dev] = gaussian_taps().to(dev)
+    sums = torch.empty(V, 3, device=dev, dtype=torch.int64)
+    maxes = torch.empty(V, 2, device=dev, dtype=torch.int32)
+    out = torch.empty(V, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(int(_lib.fn("sfx_eval_metrics_workspace_bytes")(V, H, W)), 8), dtype=torch.uint8, device=dev)
+    call("sfx_eval_metrics_u8", V, H, W, ptr(pred), ptr(gt), gs, mptr, ms, 1 if clamp_pred else 0, ptr(taps),
+         ptr(sums), ptr(maxes), ptr(out), ptr(ws), ws.numel(), stream())
+    return sums, maxes, out
+
+
+def eval_metrics_u8(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor | None = None,
+                    clamp_pred: bool = True) -> dict:
+    """PSNR and SSIM of the evaluation loop's uint8 images in one fused pass (sfx_eval_metrics_u8), with the
+    object mask of a 'real' scene (train.py:104-113, branch `gt_imgs.shape[-1] == 4`): the prediction alone is
+    multiplied by the mask before both images are truncated to uint8; the metrics run over all pixels.
+
+    pred [V,H,W,3]; gt [V,H,W,3] or [V,H,W,4].  A 4-channel gt is read in place (no slice, no copy) and its 4th
+    channel is the mask, unless `mask` ([V,H,W] or [V,H,W,1]) is given; a 3-channel gt without a mask is the
+    unmasked evaluation.  Any other shape raises ValueError.
+    Returns {"psnr": [V] float64 on the host (psnr_from_stats, with its batch-max rule), "ssim": [V] float32 on
+    the device (of the uint8 images / 255, as ssim(quantize_u8=True)), "sums": [V,3] int64, "maxes": [V,2] int32}
+    (sums / maxes as image_stats_u8)."""
+    sums, maxes, out = eval_stats_u8(pred, gt, mask, clamp_pred)
+    V = pred.shape[0]
+    psnr = psnr_from_stats(sums, maxes, pred[0].numel()) if V else torch.empty(0, dtype=torch.float64)
+    return {"psnr": psnr, "ssim": out, "sums": sums, "maxes": maxes}
