@@ -780,6 +780,51 @@ int sfx_heads_pack(int ng, int kin, int out_dim, const float* w1, int ld1, const
 int sfx_heads(int M, int ng, int kin, int out_dim, const float* x, long long ldx, int res_off, int n_tanh,
               const int* ocols, const float* stream, const float* params, float* y, void* stream_);
 
+/* (ABI 16, additive) LPIPS(net='vgg') building blocks (reference train.py:269-282, utils/metrics.py:13-17): the
+ * frozen VGG16 feature stack on NHWC fp32 images [V][H][W][C] and the tap distance, forward and data backward (no
+ * weight gradients).  The precision mode of sfx_set_precision is ignored: every product is fp32-accurate.  Every
+ * floating-point sum has one fixed order (no float atomics): two calls give equal bits.  Every entry refuses sizes
+ * < 1, NULL buffers and operands of 2 GiB or more (chunk over images) with a message and without a launch.
+ * sfx_conv3x3_pack (once per weight set): w = torch Conv2d weights [cout][cin][3][3], or with transpose_flip the
+ *   weights [cin][cout][3][3] of the layer whose data backward this convolution is (rotated by 180 degrees, in/out
+ *   transposed); packed: sfx_conv3x3_pack_bytes(cin, cout) bytes, 16-byte aligned.
+ * sfx_conv3x3: y = conv3x3(x) + bias (NULL: none), stride 1, zero padding 1; ReLU if relu; then, with mask_src
+ *   [V][H][W][cout], y *= (mask_src > 0) (the data backward of a = relu(conv(a_prev)) with mask_src = a_prev gives
+ *   the gradient of a_prev's pre-activation).  cin % 32 == 0 and cout % 64 == 0 run on MFMA (fp16 h/l operand
+ *   pairs, the activation scaled per image, weight rows by their own maxima); other shapes (cin = 3 forward,
+ *   cout = 3 backward) on the VALU.  ws: sfx_conv3x3_workspace_bytes(V) bytes, 16-byte aligned; x, y distinct.
+ * sfx_conv3x3_tile: the MFMA kernel's pixel tile (tests size their edge cases from it).
+ * sfx_maxpool2x2: y [V][H/2][W/2][C] (floor: an odd last row / column is dropped); C % 4 == 0, 16-byte aligned.
+ * sfx_maxpool2x2_bwd: dx[first maximum of each window in row-major order] += dy (dx holds the gradient that
+ *   reached x by other paths); relu_mask: only where that maximum is > 0.
+ * sfx_lpips_input: u = ((2 p - 1) - shift_c) / scale_c of p = x [V][H][W][3]; with mask [V][H][W] p = x * m first;
+ *   with quantize_u8 then p = sat_u8((int)(p * 255.f)) / 255.f (sfx_eval_metrics_u8's quantisation).  H, W >= 16
+ *   (the network pools four times).  sfx_lpips_input_bwd: dx = du * 2 / scale_c.
+ * sfx_tap_normalize: fhat = f / (sqrt(sum_c f^2) + 1e-10) per pixel of f [pixels][C].
+ * sfx_tap_dist: out[v] (+= if accumulate) mean over the image's pixels of sum_c w_c (fhat_x - fhat_y)^2, fx
+ *   unnormalised; ws: sfx_tap_dist_workspace_bytes bytes, 4-byte aligned.
+ * sfx_tap_dist_bwd: dfx = image_scale[v] * d/d fx of the image's pixel SUM (pass upstream / pixels_per_image);
+ *   relu_mask: zero where fx <= 0 (fx a ReLU output: the gradient of its pre-activation). */
+int sfx_conv3x3_tile(int* tile_h, int* tile_w);
+size_t sfx_conv3x3_pack_bytes(int cin, int cout);
+int sfx_conv3x3_pack(int cin, int cout, const float* w, int transpose_flip, void* packed, void* stream);
+size_t sfx_conv3x3_workspace_bytes(int num_images);
+int sfx_conv3x3(int num_images, int height, int width, int cin, int cout, const float* x, const void* packed,
+                const float* bias, const float* mask_src, int relu, float* y, void* ws, size_t ws_bytes,
+                void* stream);
+int sfx_maxpool2x2(int num_images, int height, int width, int channels, const float* x, float* y, void* stream);
+int sfx_maxpool2x2_bwd(int num_images, int height, int width, int channels, const float* x, const float* dy,
+                       int relu_mask, float* dx, void* stream);
+int sfx_lpips_input(int num_images, int height, int width, const float* x, const float* mask, int quantize_u8,
+                    float* u, void* stream);
+int sfx_lpips_input_bwd(int num_images, int height, int width, const float* du, float* dx, void* stream);
+int sfx_tap_normalize(long long pixels, int channels, const float* f, float* fhat, void* stream);
+size_t sfx_tap_dist_workspace_bytes(int num_images, long long pixels_per_image);
+int sfx_tap_dist(int num_images, long long pixels_per_image, int channels, const float* fx, const float* fhat_y,
+                 const float* w, int accumulate, float* out, void* ws, size_t ws_bytes, void* stream);
+int sfx_tap_dist_bwd(int num_images, long long pixels_per_image, int channels, const float* fx, const float* fhat_y,
+                     const float* w, const float* image_scale, int relu_mask, float* dfx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ For each scene of this rank's chunk (dataset/GS.py:54-67): refine with the Featu
 per forward, feature_predictor.py:244), render the V test views of the refined Gaussians
 (gs_utils.rasterize_gaussians_to_multiimgs), quantise prediction and target to uint8 and accumulate the
 per-image PSNR and SSIM sums (train.py:104-131, utils/metrics.py); finally reduce to rank 0
-(train.py:170-176).  LPIPS (VGG weights, unavailable offline) is out of scope.
+(train.py:170-176).  With `lpips=` (an lpips.LPIPS built from a VGG weight file the user supplies) the third
+column of the reference's eval.csv, LPIPS (utils/metrics.py:13-17), is computed on the same quantised images.
 
 Masked branch (train.py:104-109, 'real' scenes): a target with a fourth channel (dataset/GS.py:128-151, the
 object mask appended by scene_io.read_image) takes `pred = pred * mask` before the uint8 truncation; the target
@@ -36,9 +37,20 @@ def _score(pred: torch.Tensor, gt: torch.Tensor) -> Tuple[torch.Tensor, torch.Te
     return psnr, ssim(pred, gt, quantize_u8=True).double().cpu()
 
 
-def _record(results: Optional[dict], name: str, psnr: torch.Tensor, ssim_: torch.Tensor) -> None:
+def _lpips(net, pred: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
+    """Per-image LPIPS, float64 on the host, on the uint8-quantised images / 255; an RGBA target's mask multiplies
+    the prediction first (train.py:104-113, metrics.py:26-29)."""
+    if gt.shape[-1] == 4:
+        return net(pred, gt[..., :3].contiguous(), quantize_u8=True, mask=gt[..., 3].contiguous()).double().cpu()
+    return net(pred, gt, quantize_u8=True).double().cpu()
+
+
+def _record(results: Optional[dict], name: str, psnr: torch.Tensor, ssim_: torch.Tensor,
+            lpips_: Optional[torch.Tensor] = None) -> None:
     if results is not None:
         results[name] = {"psnr": psnr.tolist(), "ssim": ssim_.tolist()}
+        if lpips_ is not None:
+            results[name]["lpips"] = lpips_.tolist()
 
 
 @torch.no_grad()
@@ -46,7 +58,7 @@ def evaluate_scenes(model, scenes: Sequence[dict], cameras: Sequence[dict],
                     targets: Callable[[int], torch.Tensor], device: torch.device,
                     evaluate_input: bool = False, *, results: Optional[dict] = None,
                     names: Optional[Sequence[str]] = None, compare_with_input: bool = False,
-                    results_input: Optional[dict] = None) -> Dict[str, float]:
+                    results_input: Optional[dict] = None, lpips=None) -> Dict[str, float]:
     """Evaluate this rank's chunk of `scenes`.
 
     scenes[i]: normalized Gaussian dict (device tensors); cameras[i]: camera dict (device tensors);
@@ -59,10 +71,14 @@ def evaluate_scenes(model, scenes: Sequence[dict], cameras: Sequence[dict],
     (train.py:127-136); the return value gains "psnr_input" and "ssim_input", reduced like the others.  Its
     per-image record goes to a second dict, `results_input` (same layout; the reference's
     metrics_input.rank{r}.json), not under a key of `results`.
+    lpips: an lpips.LPIPS; the return value and the records gain "lpips" (and "lpips_input" with
+    compare_with_input).  Without it the keys are "psnr" and "ssim" only.
     Returns the rank-0 reduced means ({} on other ranks)."""
     rank, ws = dist.world()
     mine = dist.scene_chunk(len(scenes), rank, ws)
     keys = ("psnr", "ssim") + (("psnr_input", "ssim_input") if compare_with_input else ())
+    if lpips is not None:
+        keys += ("lpips",) + (("lpips_input",) if compare_with_input else ())
     total = {k: torch.zeros((), dtype=torch.float64) for k in keys}
     num_images = 0
     for i in mine:
@@ -72,16 +88,23 @@ def evaluate_scenes(model, scenes: Sequence[dict], cameras: Sequence[dict],
         gt = targets(i)
         name = str(i) if names is None else names[i]
         psnr, ssim_ = _score(pred, gt)
+        lp = _lpips(lpips, pred, gt) if lpips is not None else None
         total["psnr"] += psnr.sum()
         total["ssim"] += ssim_.sum()
-        _record(results, name, psnr, ssim_)
+        if lp is not None:
+            total["lpips"] += lp.sum()
+        _record(results, name, psnr, ssim_, lp)
         if compare_with_input:
             if not evaluate_input:  # otherwise the prediction IS the input's render
                 rgbs, _ = rasterize_gaussians_to_multiimgs(scenes[i], cameras[i])
-                psnr, ssim_ = _score(torch.stack(rgbs, 0), gt)
+                pred_in = torch.stack(rgbs, 0)
+                psnr, ssim_ = _score(pred_in, gt)
+                lp = _lpips(lpips, pred_in, gt) if lpips is not None else None
             total["psnr_input"] += psnr.sum()
             total["ssim_input"] += ssim_.sum()
-            _record(results_input, name, psnr, ssim_)
+            if lp is not None:
+                total["lpips_input"] += lp.sum()
+            _record(results_input, name, psnr, ssim_, lp)
         num_images += pred.shape[0]
         if not evaluate_input and hasattr(model, "check_refine"):
             model.check_refine()  # the refine's deferred pooling checks, at the readback that consumes it

@@ -2,8 +2,8 @@
 (csrc/loss.hip, sfx_image_loss).
 
 The L1 term is the reference's image_l1 (train.py:275-280); the D-SSIM term uses the reference's own SSIM
-(utils/metrics.py:93-135, the one `metrics.ssim` evaluates) and stands in for the LPIPS term, whose VGG weights
-cannot be had offline.  Forward and derivative come from one kernel call; there is no CPU fallback.
+(utils/metrics.py:93-135, the one `metrics.ssim` evaluates); the reference's LPIPS term is lpips.py's, on VGG
+weights the user supplies.  Forward and derivative come from one kernel call; there is no CPU fallback.
 
 `image_loss_and_grad` is the direct form for a caller that knows the upstream scale of every view (the Trainer);
 `image_loss` wraps it as an autograd function.

@@ -4,8 +4,9 @@ Per scene: FeaturePredictor forward in train mode (ptv3_train), the refined Gaus
 training views through the gsplat-compatible autograd path (gs_render / gsplat_compat HIP kernels; or, with
 render="batched", through the eval path's single batched pass and its two-launch backward), the
 image L1 loss `sum_v |pred_v - gt_v|.mean() / num_images / len(batch)` (train.py:272-283, image_l1 weight 1;
-the LPIPS term needs VGG weights that are not available offline and is left out; Trainer(ssim_loss_weight=...)
-adds a D-SSIM term `1 - SSIM` in its place, losses.py / csrc/loss.hip), backward through the
+Trainer(lpips_loss_weight=..., lpips=LPIPS.from_files(...)) adds the reference's LPIPS term on VGG weights the
+user supplies, lpips.py / csrc/lpips.hip, off by default because no weights are shipped; Trainer(ssim_loss_weight=...)
+adds a D-SSIM term `1 - SSIM`, losses.py / csrc/loss.hip), backward through the
 renderer to the packed refined record, then the hand-written refiner backward.  Every `accumulate_step`
 micro-steps: gradient all-reduce (DDP average, one flat bucket over RCCL), clip_grad_norm_(2.0) and
 Adam(lr 3e-5, eps 1e-15) on the trainable parameters (by default attn.qkv, utils/optimizers.py:48-52,
@@ -22,6 +23,7 @@ from torch import Tensor
 
 from . import _lib
 from . import losses
+from . import lpips as lpips_mod
 from . import ptv3_ops as ops
 from . import ptv3_train as pt
 from . import train_ops as tops
@@ -188,15 +190,19 @@ class Trainer:
     def __init__(self, model: FeaturePredictor, lr=3e-5, eps: float = 1e-15, betas=(0.9, 0.999),
                  grad_clip_norm: float = 2.0, accumulate_step: int = 1, group=None, generator=None,
                  precision: Optional[str] = None, render: Optional[str] = None, finetune_list=("attn.qkv",),
-                 image_l1_loss_weight: float = 1.0, ssim_loss_weight: float = 0.0):
-        """image_l1_loss_weight, ssim_loss_weight: the per-view loss is
-        `image_l1_loss_weight * mean|p - g| + ssim_loss_weight * (1 - SSIM(p, g))`, summed over the views and divided
-        by num_images, len(scenes) and accumulate_step (the normalisation the reference gives image_l1 and its LPIPS
-        term, train.py:277-286).  The L1 weight is the reference's (train.py:206, default 1); the D-SSIM term
-        (the reference's own SSIM, utils/metrics.py:93-135) stands in for the LPIPS term and is off by default.  With
-        ssim_loss_weight == 0 the loss is the torch image_l1; above 0 one losses.image_loss_and_grad call per
+                 image_l1_loss_weight: float = 1.0, ssim_loss_weight: float = 0.0, lpips_loss_weight: float = 0.0,
+                 lpips=None):
+        """image_l1_loss_weight, ssim_loss_weight, lpips_loss_weight: the per-view loss is
+        `image_l1_loss_weight * mean|p - g| + ssim_loss_weight * (1 - SSIM(p, g)) + lpips_loss_weight * LPIPS(p, g)`,
+        summed over the views and divided by num_images, len(scenes) and accumulate_step (the normalisation the
+        reference gives image_l1 and its LPIPS term, train.py:277-286).  The L1 weight is the reference's
+        (train.py:206, default 1).  The LPIPS term is the reference's (training.lpips_loss_weight, default 1 there;
+        0 here, because it needs `lpips`, an lpips.LPIPS built from a weight file the user supplies: a weight above 0
+        without one raises).  Its weights are frozen and are no part of state_dict.  The D-SSIM term (the
+        reference's own SSIM, utils/metrics.py:93-135) is an option of this project and off by default.  With
+        ssim_loss_weight == 0 the L1 term is the torch image_l1; above 0 one losses.image_loss_and_grad call per
         scene computes loss and derivative, and `last_metrics` holds the batch's image_l1, ssim and train_psnr
-        (train.py:278, :283) as device tensors.
+        (train.py:278, :283) as device tensors; with the LPIPS term it also holds "lpips".
         precision: "fp32" (default; fp32-accurate refiner forward + backward) or "amp", the reference's
         `training.enable_amp` (train.py:214-299, configs/train/default.gin:11): refiner forward and backward in
         the autocast precision class (ptv3_ops.precision); the renderer, loss and optimiser stay fp32 as in the
@@ -218,9 +224,17 @@ class Trainer:
         if not (image_l1_loss_weight >= 0.0 and ssim_loss_weight >= 0.0):
             raise ValueError(f"loss weights must be >= 0, got image_l1_loss_weight {image_l1_loss_weight}, "
                              f"ssim_loss_weight {ssim_loss_weight}")
+        if not lpips_loss_weight >= 0.0:
+            raise ValueError(f"loss weights must be >= 0, got lpips_loss_weight {lpips_loss_weight}")
+        if lpips_loss_weight > 0.0 and lpips is None:
+            raise ValueError("lpips_loss_weight > 0 needs `lpips`, an lpips.LPIPS built from a VGG weight file "
+                             "(LPIPS.from_files); no weights are shipped")
         self.image_l1_loss_weight = float(image_l1_loss_weight)
         self.ssim_loss_weight = float(ssim_loss_weight)
-        self.last_metrics: Optional[Dict[str, Tensor]] = None  # filled by micro_step when ssim_loss_weight > 0
+        self.lpips_loss_weight = float(lpips_loss_weight)
+        self.lpips = lpips  # frozen, not a module: no parameter of it trains or is saved
+        # filled by micro_step when ssim_loss_weight > 0 or lpips_loss_weight > 0
+        self.last_metrics: Optional[Dict[str, Tensor]] = None
         if isinstance(finetune_list, str):
             finetune_list = (finetune_list,)
         self.finetune_list = tuple(finetune_list or ())
@@ -258,8 +272,10 @@ class Trainer:
         total = 0.0
         num_images = sum(len(im) for im in images)  # counted over the whole batch (train.py:273-281)
         fused = self.ssim_loss_weight > 0.0  # L1 + D-SSIM and its derivative from one kernel call per scene
+        with_lpips = self.lpips_loss_weight > 0.0
         norm = 1.0 / num_images / len(scenes) / self.accumulate_step
         sums = None
+        lpips_sum = None
         for gs, cams, imgs in zip(scenes, cameras, images):
             with ops.precision(self.precision):
                 packed, tape = refine_train(self.model, gs, masks, perms=perms, group=self.group)
@@ -279,8 +295,16 @@ class Trainer:
                     terms, d_pred = losses.image_loss_and_grad(
                         stacked, imgs, self.image_l1_loss_weight, self.ssim_loss_weight,
                         torch.full((len(preds),), norm, device=stacked.device, dtype=torch.float32))
-                    torch.autograd.backward(stacked, d_pred)
                     loss = terms[:, 3].sum() * norm
+                    if with_lpips:  # its derivative joins the fused one: one backward through the renderer
+                        lp, d_lp = self.lpips.value_and_grad(
+                            stacked, imgs, torch.full((len(preds),), norm * self.lpips_loss_weight,
+                                                      device=stacked.device, dtype=torch.float32))
+                        d_pred += d_lp
+                        loss = loss + lp.sum() * (norm * self.lpips_loss_weight)
+                        lpips_sum = lp.sum() if lpips_sum is None else lpips_sum + lp.sum()
+                        del d_lp
+                    torch.autograd.backward(stacked, d_pred)
                     # sums over the views of mean|p-g|, SSIM and the unquantised PSNR 20 log10(1 / sqrt(mse))
                     m = torch.stack([terms[:, 0].sum(), terms[:, 1].sum(), (-10.0 * torch.log10(terms[:, 2])).sum()])
                     sums = m if sums is None else sums + m
@@ -289,6 +313,10 @@ class Trainer:
                     loss = image_l1(preds, imgs)
                     if self.image_l1_loss_weight != 1.0:  # (the default adds no launch)
                         loss = loss * self.image_l1_loss_weight
+                    if with_lpips:
+                        lp = lpips_mod.lpips_loss(preds, imgs, self.lpips)
+                        loss = loss + lp.sum() * self.lpips_loss_weight
+                        lpips_sum = lp.detach().sum() if lpips_sum is None else lpips_sum + lp.detach().sum()
                     loss = loss / num_images / len(scenes) / self.accumulate_step
                     loss.backward()
             with ops.precision(self.precision):
@@ -299,6 +327,9 @@ class Trainer:
         if fused:  # averaged as train.py:283 averages train_psnr; device tensors, no host read
             avg = sums / num_images / len(scenes)
             self.last_metrics = {"image_l1": avg[0], "ssim": avg[1], "train_psnr": avg[2]}
+        if with_lpips:
+            self.last_metrics = dict(self.last_metrics or {}) if fused else {}
+            self.last_metrics["lpips"] = lpips_sum / num_images / len(scenes)
         loss = float(total)  # (drains the stream)
         _lib.check_lookback("Trainer.micro_step")  # the step's scans / radix passes (pooling, intersection sort)
         return loss
