@@ -33,6 +33,7 @@
 // slot), counted vmcnt, raw s_barrier (no __syncthreads: its fence would drain the DMA queue).
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <cstdlib>
 
 #include "gemm_common.h"
@@ -77,10 +78,15 @@ __device__ __forceinline__ int slab_off(int r, int q) {
 // (lgkmcnt(0)), so the slot the phase refills after the barrier is no longer being read (cdna_hip_programming.md
 // §5, "Read a staged buffer one phase AFTER the wait that retires it": a slot restaged one phase after its last
 // read needs that lgkmcnt before the barrier).
+// The wait is the builtin, not inline assembly: the compiler keeps its own count of the memory operations in flight
+// and reads a builtin wait, not assembly text.  While it believes an LDS-DMA in flight, every vmcnt wait it adds
+// comes out a full one; behind the tail's builtin vmcnt(0) lgkmcnt(0) it knows none is, and the epilogue's residual
+// loads get counted waits.  (The comment line marks the wait as written, with its count, for tools/mlp_resources.py.)
 template <int N>
 __device__ __forceinline__ void wait_vm_lgkm() {
   static_assert(N >= 0 && N <= 63, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+  asm volatile("; written wait vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x70);  // gfx9 encoding: vmcnt N, expcnt 7 (none), lgkmcnt 0
 }
 
 // One workgroup = WAVES x 32 points; wave w owns points [32 w, 32 w + 32) of the tile and computes every hidden
@@ -119,6 +125,10 @@ __device__ __forceinline__ float gelu_grad_fit(float x) {
   return phi_cdf + x * (0.39894228040143268f * __builtin_amdgcn_exp2f(-0.72134752044448170f * x * x));
 }
 
+// the anchor of the LDS-DMA destinations (mlp_kernel, `dma_base`): the dynamic LDS array, no bytes -- every launch
+// passes 0
+extern __shared__ __attribute__((aligned(16))) char mlp_dma_anchor[];
+
 // ONE (training kinds under sfx_set_precision(1), the reference's autocast class): the leading product h*h of each
 // block only (the l terms are never read: fp16-rounded operands, fp32 accumulation).
 // SPLIT > 1 (eval; the last, partial round of a launch -- sfx_block_mlp's tail): workgroup (x, s) computes the
@@ -137,11 +147,12 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
   constexpr int NB = G::NB, NP = NCHS * G::PPC, PPC = G::PPC, NT = C / 16;  // NT: fc1 k-steps
   constexpr int NTH = WAVES * 64;
   constexpr int PIECES = 16 / WAVES;  // 1 KB LDS-DMA pieces per wave per phase
-  constexpr int PAR_OFF = RING * PHASE_BYTES;
-  constexpr int LDS_BYTES = PAR_OFF + G::PAR * 4;
-  static_assert(16 % WAVES == 0 && LDS_BYTES <= 163840, "geometry");
-  __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
-  float* s_par = reinterpret_cast<float*>(lds + PAR_OFF);
+  constexpr int RING_BYTES = RING * PHASE_BYTES;
+  static_assert(16 % WAVES == 0 && RING_BYTES + G::PAR * 4 <= 163840 && G::PAR % 4 == 0, "geometry");
+  // The ring and the parameter table are two objects: LDS-DMA writes the ring only, so the compiler orders no read
+  // of the table against the DMAs in flight (one array for both cost a vmcnt(0), the whole ring, per hidden chunk).
+  __shared__ __attribute__((aligned(16))) char lds[RING_BYTES];
+  __shared__ __attribute__((aligned(16))) float s_par[G::PAR];
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int h = lane >> 5, r32 = lane & 31;
@@ -150,6 +161,17 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
   const int prow = (int)blockIdx.x * PTS + pg * 32 + r32;  // this lane's point
   const bool pok = prow < M;
 
+  // The DMA's destination is written as an offset from another LDS object (the empty dynamic array, which adds no
+  // LDS), the distance to the ring passing through an empty asm.  The compiler tracks every LDS-DMA in flight and
+  // waits for it in front of each LDS read it cannot prove disjoint (in the generated code a DMA into a lower slot
+  // counted as reaching the higher ones), and such a wait is a vmcnt(0): with the DMAs written into `lds` it drained
+  // the ring in front of a fragment read once per hidden chunk or more, wherever the table lived.  Reads of `lds`
+  // and DMAs "into" `mlp_dma_anchor` are disjoint to it; the order is kept by hand, as it always was: the counted
+  // wait and the barrier in front of every phase (RAW), lgkmcnt(0) before the barrier (WAR).
+  typedef __attribute__((address_space(3))) char lds_char;  // LDS addresses are 32 bits: the distance wraps with them
+  int ring_delta = (int)((unsigned)(size_t)(lds_char*)lds - (unsigned)(size_t)(lds_char*)mlp_dma_anchor);
+  asm volatile("" : "+s"(ring_delta));
+  lds_char* dma_base = (lds_char*)mlp_dma_anchor + ring_delta;
   // ---- weight stream: logical phase q -> ring slot q % RING; rot: each workgroup starts at its own hidden
   // chunk j0 and wraps, so the workgroups of an XCD read different parts of the stream at any moment
   const int j0 = SPLIT > 1 ? (int)blockIdx.y * NCHS : (rot ? (int)(blockIdx.x % G::NCH) : 0);
@@ -159,18 +181,23 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
     jq -= jq >= G::NCH ? G::NCH : 0;
     const int sq = jq * PPC + (q - (q / PPC) * PPC);  // stream phase of logical phase q
     const char* src = gstream + (size_t)sq * PHASE_BYTES + wid * (PIECES * 1024) + lane * 16;
-    char* dst = lds + (q % RING) * PHASE_BYTES + wid * (PIECES * 1024);
+    lds_char* dst = dma_base + (q % RING) * PHASE_BYTES + wid * (PIECES * 1024);
 #pragma unroll
     for (int pc = 0; pc < PIECES; ++pc)
       __builtin_amdgcn_global_load_lds(src + pc * 1024, (__attribute__((address_space(3))) void*)(dst + pc * 1024),
                                        16, 0, 0);
   };
-#pragma unroll
-  for (int q = 0; q < RING - 1; ++q)
-    if (q < NP) issue(q);
-
   // ---- prologue: parameter table; this lane's half row of X2, LayerNorm, fc1 B fragments, scales ----
-  for (int i = tid; i < G::PAR; i += NTH) s_par[i] = par[i];
+  // Every load the prologue waits for is issued before the first weight DMAs: vmcnt retires in order, so a load
+  // behind them would wait for RING - 1 phases of weights as well.  The table: 16-byte loads, all in flight at once.
+  constexpr int PAR4 = G::PAR / 4, NPL = (PAR4 + NTH - 1) / NTH;
+  // (no branch: threads past the end copy the last 16 bytes again -- a branch would leave the compiler one path
+  // without the load, and its wait for the others falls back to vmcnt(0))
+  // (buffer loads, as the row loads: a plain load of read-only memory the compiler may move behind the DMAs)
+  const __amdgpu_buffer_rsrc_t rP = rsrc_ext(par, (unsigned)G::PAR * 4u);
+  float4 pv[NPL];
+#pragma unroll
+  for (int k = 0; k < NPL; ++k) pv[k] = bload4(rP, (unsigned)min(tid + k * NTH, PAR4 - 1) * 16u);
   const __amdgpu_buffer_rsrc_t rX = rsrc_ext(X, (unsigned)M * (unsigned)ldx * 4u);
   const unsigned xr = (unsigned)prow * (unsigned)ldx;
   float4 v[2 * NT];  // channels 16 t + 8 h + 0..3 (v[2t]) and + 4..7 (v[2t+1])
@@ -182,6 +209,11 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
   }
   // the DropPath keep factor of this point (training kinds; 1 without a mask, 0 past M)
   const float rsp = (KIND != MLP_EVAL && rowscale) ? (pok ? rowscale[prow] : 0.f) : 1.f;
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int q = 0; q < RING - 1; ++q)
+    if (q < NP) issue(q);
+  __builtin_amdgcn_sched_barrier(0);
   float mean = 0.f, rstd = 1.f;
   if constexpr (KIND != MLP_BWD) {
     float sm = 0.f;
@@ -198,6 +230,9 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
     q2 += __shfl_xor(q2, 32, 64);
     rstd = 1.f / sqrtf(q2 / (float)C + eps);
   }
+#pragma unroll
+  for (int k = 0; k < NPL; ++k)
+    reinterpret_cast<float4*>(s_par)[min(tid + k * NTH, PAR4 - 1)] = pv[k];
   __syncthreads();  // s_par visible (no DMA is waited for here: only plain stores precede it)
   float mx = 0.f, nrm = 0.f;
 #pragma unroll
@@ -286,6 +321,8 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
           // Z row of this lane's point: registers 4 q .. 4 q + 3 are units 64 j + 32 cb' + 8 q + 4 h + 0..3
           float* zrow = Z + (size_t)(pok ? prow : 0) * (4 * C) + 64 * j + 32 * (HS ? cn : cb) + 4 * h;
           if constexpr (KIND == MLP_BWD) {
+            // (the wait for Z came out a vmcnt(0) wherever the loads were issued, as every vmcnt wait the compiler
+            // adds while an LDS-DMA is in flight -- the backward kinds keep one drain of the ring per chunk)
             float4 zq[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q)
@@ -340,20 +377,30 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
     }
   };
 
-  int p = 0;
-  for (int jl = 0; jl < NCHS; ++jl) {
+  // One hidden chunk.  ALL: every phase of it refills the ring (the chunks of the main loop); else jl is a
+  // compile-time number (the unrolled last chunks) and each phase knows whether it still refills.  No phase
+  // branches at run time: where a path that refilled joins one that did not, the compiler's count of the memory
+  // operations in flight falls back to "none behind the oldest", and its next wait for a load becomes vmcnt(0).
+  auto chunk = [&](auto all, int jl) {
+    constexpr bool ALL = decltype(all)::value;
     const int j = jl + j0 - (jl + j0 >= G::NCH ? G::NCH : 0);  // the hidden chunk of this logical chunk
 #pragma unroll
     for (int cb = 0; cb < (HS ? 1 : 2); ++cb)
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc1[cb][i] = 0.f;
 #pragma unroll
-    for (int pi = 0; pi < PPC; ++pi, ++p) {
-      if (p + RING - 1 < NP) wait_vm_lgkm<(RING - 2) * PIECES>();
-      else wait_vm_lgkm<0>();  // tail: nothing younger than this phase in flight
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");  // no LDS access moves across the barrier
-      if (p + RING - 1 < NP) issue(p + RING - 1);  // refills the slot every wave finished before the barrier
+    for (int pi = 0; pi < PPC; ++pi) {
+      const int p = jl * PPC + pi;
+      if (ALL || p + RING - 1 < NP) {
+        wait_vm_lgkm<(RING - 2) * PIECES>();
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");  // no LDS access moves across the barrier
+        issue(p + RING - 1);            // refills the slot every wave finished before the barrier
+      } else {
+        wait_vm_lgkm<0>();  // tail: nothing younger than this phase in flight
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+      }
       const char* base = lds + (p % RING) * PHASE_BYTES;
       f16x8 fa0[2][2][2], fa1[2][2][2];
       load_frags(base, fa0);
@@ -361,8 +408,35 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
       slab(fa0, 2 * pi, j);
       slab(fa1, 2 * pi + 1, j);
     }
-  }
+  };
+  // the chunks whose every phase refills: phases p with p + RING - 1 < NP
+  constexpr int NMAIN = NP >= RING - 1 ? (NP - (RING - 1)) / PPC : 0;
+#pragma unroll 1
+  for (int jl = 0; jl < NMAIN; ++jl) chunk(std::true_type{}, jl);
+#pragma unroll
+  for (int jl = NMAIN; jl < NCHS; ++jl) chunk(std::false_type{}, jl);
 
+  // ---- epilogue: Y = X2 + acc2 / (t s_c) + b2, 16 bytes of 4 consecutive channels per lane and access ----
+  // Three straight runs: every residual load of the wave (into the registers the fc1 fragments leave free), then
+  // the finished values in place of acc2 as the loads come back in order, then every store.  vmcnt counts stores
+  // too, so a load issued behind a store would wait for that store's acknowledgement: one round trip per step.
+  // A lane loads exactly the elements it stores later and finishes them from the loaded values, so X may be Y.
+  constexpr bool RESID = SPLIT == 1 && KIND != MLP_BWD;
+  // SPLIT > 1: the output is plane blockIdx.y of P [SPLIT][M][C] (M C 4 <= M ldx 4 bytes: within a descriptor)
+  const __amdgpu_buffer_rsrc_t rY = SPLIT > 1 ? rsrc_ext(P + (size_t)blockIdx.y * M * C, (unsigned)M * (unsigned)C * 4u)
+                                              : rsrc_ext(Y, (unsigned)M * (unsigned)ldy * 4u);
+  const unsigned yr = (unsigned)prow * (SPLIT > 1 ? (unsigned)C : (unsigned)ldy);
+  float4 xres[RESID ? NB * 4 : 1];
+  auto load_residual = [&]() {
+    if constexpr (RESID) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4)
+          xres[b * 4 + g4] = bload4(rX, pok ? (xr + (unsigned)(32 * b + 8 * g4 + 4 * h)) * 4u : OOB);
+      __builtin_amdgcn_sched_barrier(0);  // no load sinks into the run of finished values
+    }
+  };
   if constexpr (HS) {  // the cn = 1 wave's partial fc2 sums -> LDS (the drained ring) -> added by its cn = 0 partner
     static_assert((WAVES / 2) * 64 * NB * 16 * 4 <= RING * PHASE_BYTES, "HS exchange fits the ring");
     __builtin_amdgcn_s_barrier();  // every wave's last ring reads are done (the tail waited for every DMA)
@@ -378,6 +452,7 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
     }
     __syncthreads();
     if (cn == 1) return;
+    load_residual();  // in flight under the exchange reads
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -388,10 +463,9 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
         acc2[b][4 * q + 2] += o.z;
         acc2[b][4 * q + 3] += o.w;
       }
+  } else {
+    load_residual();
   }
-  // ---- epilogue: Y = X2 + acc2 / (t s_c) + b2, 16-byte stores of 4 consecutive channels ----
-  const __amdgpu_buffer_rsrc_t rY = rsrc_ext(Y, (unsigned)M * (unsigned)ldy * 4u);
-  const unsigned yr = (unsigned)prow * (unsigned)ldy;
   float ymax = 0.f;  // MLP_EVAL with Z: this point's max |Y| -> the next fused SubM conv's row exponent
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
@@ -399,7 +473,6 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
       const float4 w01 = pp[2 * g4], w23 = pp[2 * g4 + 1];  // (1/s_c, b2_c) of registers 4 g4 .. 4 g4 + 3
-      const unsigned c0 = (unsigned)(32 * b + 8 * g4 + 4 * h);
       float4 y;
       if constexpr (SPLIT > 1) {  // this split's branch partial (b2 carried by split 0) -> P[s][prow]
         const float bb = (KIND != MLP_BWD && blockIdx.y == 0) ? 1.f : 0.f;
@@ -408,25 +481,34 @@ __global__ void __launch_bounds__(WAVES * 64, (WAVES == 4 && C > 128) ? 1 : 2)
         y.y = rr * (acc2[b][4 * g4 + 1] * (tinv * w01.z) + bb * w01.w);
         y.z = rr * (acc2[b][4 * g4 + 2] * (tinv * w23.x) + bb * w23.y);
         y.w = rr * (acc2[b][4 * g4 + 3] * (tinv * w23.z) + bb * w23.w);
-        if (pok)
-          *reinterpret_cast<float4*>(P + ((size_t)blockIdx.y * M + prow) * C + c0) = y;
-        continue;
       } else if constexpr (KIND == MLP_BWD) {  // the branch's input gradient: no bias, no residual
         y.x = acc2[b][4 * g4 + 0] * (tinv * w01.x);
         y.y = acc2[b][4 * g4 + 1] * (tinv * w01.z);
         y.z = acc2[b][4 * g4 + 2] * (tinv * w23.x);
         y.w = acc2[b][4 * g4 + 3] * (tinv * w23.z);
       } else {
-        const float4 xres = bload4(rX, pok ? (xr + c0) * 4u : OOB);
-        y.x = xres.x + rsp * (acc2[b][4 * g4 + 0] * (tinv * w01.x) + w01.y);
-        y.y = xres.y + rsp * (acc2[b][4 * g4 + 1] * (tinv * w01.z) + w01.w);
-        y.z = xres.z + rsp * (acc2[b][4 * g4 + 2] * (tinv * w23.x) + w23.y);
-        y.w = xres.w + rsp * (acc2[b][4 * g4 + 3] * (tinv * w23.z) + w23.w);
+        const float4 xv = xres[b * 4 + g4];
+        y.x = xv.x + rsp * (acc2[b][4 * g4 + 0] * (tinv * w01.x) + w01.y);
+        y.y = xv.y + rsp * (acc2[b][4 * g4 + 1] * (tinv * w01.z) + w01.w);
+        y.z = xv.z + rsp * (acc2[b][4 * g4 + 2] * (tinv * w23.x) + w23.y);
+        y.w = xv.w + rsp * (acc2[b][4 * g4 + 3] * (tinv * w23.z) + w23.w);
       }
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rY, pok ? (yr + c0) * 4u : OOB, 0, 0);
+      acc2[b][4 * g4 + 0] = y.x;
+      acc2[b][4 * g4 + 1] = y.y;
+      acc2[b][4 * g4 + 2] = y.z;
+      acc2[b][4 * g4 + 3] = y.w;
       if constexpr (KIND == MLP_EVAL) ymax = fmaxf(ymax, fmaxf(fmaxf(fabsf(y.x), fabsf(y.y)), fmaxf(fabsf(y.z), fabsf(y.w))));
     }
   }
+  __builtin_amdgcn_sched_barrier(0);  // the stores in one run, behind every load and every finished value
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+      const unsigned c0 = (unsigned)(32 * b + 8 * g4 + 4 * h);
+      const float4 y = make_float4(acc2[b][4 * g4], acc2[b][4 * g4 + 1], acc2[b][4 * g4 + 2], acc2[b][4 * g4 + 3]);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rY, pok ? (yr + c0) * 4u : OOB, 0, 0);
+    }
   if constexpr (KIND == MLP_EVAL && SPLIT == 1) {
     // sfx_subm_rowexp of the output row (csrc/subm_fused.hip, same rule): max in [2^14, 2^15), 127 for a zero row,
     // 0 for inf / nan -- the next Block's fused conv reads it instead of re-reading the row
@@ -854,7 +936,9 @@ int sfx_block_mlp(int M, int C, const float* x, long long ldx, const float* stre
               "sfx_block_mlp: buffers must be 16-byte aligned");
   SFX_REQUIRE((long long)M * ldx * 4 + 64 < (long long)OOB && (long long)M * ldy * 4 + 64 < (long long)OOB,
               "sfx_block_mlp: operand exceeds the 2 GiB buffer-descriptor range");
-  SFX_REQUIRE(x != y, "sfx_block_mlp: in-place output is not supported");
+  // y == x (same leading dimension) is served: every lane finishes the elements it stores from values it loaded
+  // itself (the kernel's epilogue, the combine of a split tail), and no other lane reads them after the prologue
+  SFX_REQUIRE(x != y || ldx == ldy, "sfx_block_mlp: in-place output needs ldx == ldy");
   hipStream_t st = sfx::as_stream(stream_);
   // C <= 128: 4-wave (128-point) workgroups, two per CU -- measured 1.0-1.2x faster than one 8-wave workgroup
   // (profiles/r04_mlp_waves_hs.txt); SFX_MLP_WAVES=8 restores the 256-point workgroups.  Hidden split (a wave pair
