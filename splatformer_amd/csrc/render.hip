@@ -6,13 +6,16 @@
 // see SURVEY.md Appendix A.2 and oracle/gsplat_ref.py for the restatement.
 // Layout: AoS float records exactly as the gsplat tensors ([N,3] means, [N,4]
 // quats (w,x,y,z), [N,2] xys, [N,3] conics ...), so the drop-in shim can hand
-// torch tensors straight through.  One workgroup of bw*bw lanes (4 waves at
-// bw=16) per 16x16 tile; per-batch Gaussian records staged in LDS.
+// torch tensors straight through.  The tile compositor itself is rasterize.hip.
 #include <climits>
 
-#include "common.h"
+#include "raster_common.h"
 
 namespace {
+
+using sfxr::CullG;
+using sfxr::cull_box_may_hit;
+using sfxr::cull_setup;
 
 __constant__ float SH_C0 = 0.28209479177387814f;
 __constant__ float SH_C1 = 0.4886025119029199f;
@@ -452,14 +455,9 @@ __global__ void __launch_bounds__(256) render_prep_project_kernel(
     }
     project_point(i, px, py, pz, sc0, sc1, sc2, q0, q1, q2, q3, 1.f, vm, fx, fy, cx, cy, img_h, img_w, bw, 0.01f,
                   xys + 2 * o, depths + o, radii + o, conics + 3 * o, nullptr, num_tiles_hit + o, nullptr);
-    if (rec) {  // the rasterizer's packed record (pack_raster_records_kernel's layout), from this thread's own stores
+    if (rec) {  // the rasterizer's packed record, from this thread's own stores
       const long long r = o + i;
-      const float* xy = xys + 2 * r;
-      const float* cn = conics + 3 * r;
-      const float* cl = rgbs + 3 * r;
-      rec[4 * r + 0] = make_float4(xy[0], xy[1], op, cn[0]);
-      rec[4 * r + 1] = make_float4(cn[1], cn[2], cl[0], cl[1]);
-      rec[4 * r + 2] = make_float4(cl[2], 0.f, 0.f, 0.f);
+      sfxr::write_record(rec, r, xys + 2 * r, op, conics + 3 * r, rgbs + 3 * r);
     }
   }
 }
@@ -817,258 +815,6 @@ __global__ void tile_bins_kernel(int num_isect, const int64_t* __restrict__ isec
   }
 }
 
-// ---- rasterize forward ------------------------------------------------------
-constexpr int MAX_BLOCK = 256;
-
-__global__ void __launch_bounds__(MAX_BLOCK)
-rasterize_fwd_kernel(int tiles_x, int tiles_y, int bw, int img_h, int img_w,
-                     const int32_t* __restrict__ gids_sorted, const int* __restrict__ tile_bins,
-                     const float* __restrict__ xys, const float* __restrict__ conics,
-                     const float* __restrict__ colors, const float* __restrict__ opacity,
-                     const float* __restrict__ background, float* __restrict__ final_Ts,
-                     int* __restrict__ final_idx, float* __restrict__ out_img, float* __restrict__ out_alpha,
-                     int clamp_max1) {
-  __shared__ int id_batch[MAX_BLOCK];
-  __shared__ float4 xyo_batch[MAX_BLOCK];   // x, y, opacity, pad
-  __shared__ float4 conic_batch[MAX_BLOCK]; // a, b, c, pad
-  __shared__ float4 rgb_batch[MAX_BLOCK];
-
-  // batched views: blockIdx.z = view (tiles numbered per view, per-view image planes)
-  const int tile_id = blockIdx.z * tiles_x * tiles_y + blockIdx.y * tiles_x + blockIdx.x;
-  if (blockIdx.z > 0) {
-    const long long po = (long long)blockIdx.z * img_h * img_w;
-    final_Ts += po; final_idx += po; out_img += 3 * po;
-    if (out_alpha) out_alpha += po;
-  }
-  const int tr = threadIdx.x;  // flat thread rank, row-major over (ty, tx)
-  const int ty = tr / bw, tx = tr - (tr / bw) * bw;
-  const int block_size = bw * bw;
-  const unsigned pi = blockIdx.y * bw + ty, pj = blockIdx.x * bw + tx;
-  const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
-  const bool inside = (pi < (unsigned)img_h && pj < (unsigned)img_w);
-  bool done = !inside;
-
-  const int range_x = tile_bins[2 * tile_id], range_y = tile_bins[2 * tile_id + 1];
-  const int num_batches = (range_y - range_x + block_size - 1) / block_size;
-
-  float T = 1.f;
-  int cur_idx = 0;
-  float r0 = 0.f, r1 = 0.f, r2 = 0.f;
-  for (int b = 0; b < num_batches; ++b) {
-    // resync before overwriting the batch; early exit when the whole tile is done
-    if (__syncthreads_count(done) >= block_size) break;
-
-    const int batch_start = range_x + block_size * b;
-    const int idx = batch_start + tr;
-    if (idx < range_y) {
-      const int g = gids_sorted[idx];
-      id_batch[tr] = g;
-      xyo_batch[tr] = make_float4(xys[2 * g], xys[2 * g + 1], opacity[g], 0.f);
-      conic_batch[tr] = make_float4(conics[3 * g], conics[3 * g + 1], conics[3 * g + 2], 0.f);
-      rgb_batch[tr] = make_float4(colors[3 * g], colors[3 * g + 1], colors[3 * g + 2], 0.f);
-    }
-    __syncthreads();
-    const int batch_size = min(block_size, range_y - batch_start);
-    for (int t = 0; (t < batch_size) && !done; ++t) {
-      const float4 con = conic_batch[t];
-      const float4 xyo = xyo_batch[t];
-      const float dx = xyo.x - px, dy = xyo.y - py;
-      const float sigma = 0.5f * (con.x * dx * dx + con.z * dy * dy) + con.y * dx * dy;
-      const float alpha = fminf(0.999f, xyo.z * __expf(-sigma));
-      if (sigma < 0.f || alpha < 1.f / 255.f) continue;
-      const float next_T = T * (1.f - alpha);
-      if (next_T <= 1e-4f) {
-        done = true;
-        break;
-      }
-      const float vis = alpha * T;
-      const float4 c = rgb_batch[t];
-      r0 = r0 + c.x * vis;
-      r1 = r1 + c.y * vis;
-      r2 = r2 + c.z * vis;
-      T = next_T;
-      cur_idx = batch_start + t;
-    }
-  }
-  if (inside) {
-    const int pix = pi * img_w + pj;
-    final_Ts[pix] = T;
-    final_idx[pix] = cur_idx;
-    float o0 = r0 + T * background[0], o1 = r1 + T * background[1], o2 = r2 + T * background[2];
-    if (clamp_max1) {  // gs_utils.py:111 torch.clamp(rgb, max=1), fused for the eval path
-      o0 = fminf(o0, 1.f); o1 = fminf(o1, 1.f); o2 = fminf(o2, 1.f);
-    }
-    out_img[3 * pix + 0] = o0;
-    out_img[3 * pix + 1] = o1;
-    out_img[3 * pix + 2] = o2;
-    if (out_alpha) out_alpha[pix] = 1.f - T;
-  }
-}
-
-// ---- packed records (eval path) ------------------------------------------------
-// One 48-byte record per projected Gaussian, written once per view batch: r0 = (x, y, opacity, conic.a),
-// r1 = (conic.b, conic.c, r, g), r2 = (b, 0, 0, 0), at a 64-byte stride (one 64-byte sector per record gather; at
-// 48 bytes two of every four records straddle a sector boundary: 1.5 sectors fetched per 36 bytes used).  The rasterizer's per-batch fetch is one gather of a
-// 16-byte-aligned record instead of four gathers from four arrays (xys 8 B, opacity 4 B, conics 12 B,
-// colours 12 B).  Measured: the same kernel time as the four-array form (config E 2285 vs 2278 us for 9
-// 1920x1080 views) -- the rasterizer is not bound by its gathers.  A wave-uniform skip of Gaussians whose
-// alpha >= 1/255 ellipse misses the wave's 16 x 4 pixels (exact, extents in r2) was 25 % slower (2855 us) and
-// is not kept.
-__global__ void pack_raster_records_kernel(int n, const float* __restrict__ xys, const float* __restrict__ conics,
-                                           const float* __restrict__ colors, const float* __restrict__ opacity,
-                                           float4* __restrict__ rec) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  rec[4 * i + 0] = make_float4(xys[2 * i], xys[2 * i + 1], opacity[i], conics[3 * i]);
-  rec[4 * i + 1] = make_float4(conics[3 * i + 1], conics[3 * i + 2], colors[3 * i], colors[3 * i + 1]);
-  rec[4 * i + 2] = make_float4(colors[3 * i + 2], 0.f, 0.f, 0.f);
-}
-
-// rasterize_fwd_kernel over packed records: the same per-pixel arithmetic in the same order (bit-identical
-// outputs); the batch is staged in LDS as the records themselves and r2 (blue) is read only for Gaussians
-// that pass the alpha test.
-__global__ void __launch_bounds__(MAX_BLOCK)
-rasterize_fwd_packed_kernel(int tiles_x, int tiles_y, int bw, int img_h, int img_w,
-                            const int32_t* __restrict__ gids_sorted, const int* __restrict__ tile_bins,
-                            const float4* __restrict__ rec, const float* __restrict__ background,
-                            float* __restrict__ final_Ts, int* __restrict__ final_idx, float* __restrict__ out_img,
-                            float* __restrict__ out_alpha, int clamp_max1) {
-  __shared__ float4 r0_batch[MAX_BLOCK];
-  __shared__ float4 r1_batch[MAX_BLOCK];
-  __shared__ float r2_batch[MAX_BLOCK];
-
-  const int tile_id = blockIdx.z * tiles_x * tiles_y + blockIdx.y * tiles_x + blockIdx.x;
-  if (blockIdx.z > 0) {
-    const long long po = (long long)blockIdx.z * img_h * img_w;
-    final_Ts += po; final_idx += po; out_img += 3 * po;
-    if (out_alpha) out_alpha += po;
-  }
-  const int tr = threadIdx.x;
-  const int ty = tr / bw, tx = tr - (tr / bw) * bw;
-  const int block_size = bw * bw;
-  const unsigned pi = blockIdx.y * bw + ty, pj = blockIdx.x * bw + tx;
-  const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
-  const bool inside = (pi < (unsigned)img_h && pj < (unsigned)img_w);
-  bool done = !inside;
-
-  const int range_x = tile_bins[2 * tile_id], range_y = tile_bins[2 * tile_id + 1];
-  const int num_batches = (range_y - range_x + block_size - 1) / block_size;
-
-  float T = 1.f;
-  int cur_idx = 0;
-  float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-  for (int b = 0; b < num_batches; ++b) {
-    if (__syncthreads_count(done) >= block_size) break;
-    const int batch_start = range_x + block_size * b;
-    const int idx = batch_start + tr;
-    if (idx < range_y) {
-      const long long g = gids_sorted[idx];
-      r0_batch[tr] = rec[4 * g];
-      r1_batch[tr] = rec[4 * g + 1];
-      r2_batch[tr] = reinterpret_cast<const float*>(rec + 4 * g + 2)[0];
-    }
-    __syncthreads();
-    const int batch_size = min(block_size, range_y - batch_start);
-    for (int t = 0; (t < batch_size) && !done; ++t) {
-      const float4 a = r0_batch[t];
-      const float4 q = r1_batch[t];
-      const float dx = a.x - px, dy = a.y - py;
-      const float sigma = 0.5f * (a.w * dx * dx + q.y * dy * dy) + q.x * dx * dy;
-      const float alpha = fminf(0.999f, a.z * __expf(-sigma));
-      if (sigma < 0.f || alpha < 1.f / 255.f) continue;
-      const float next_T = T * (1.f - alpha);
-      if (next_T <= 1e-4f) {
-        done = true;
-        break;
-      }
-      const float vis = alpha * T;
-      c0 = c0 + q.z * vis;
-      c1 = c1 + q.w * vis;
-      c2 = c2 + r2_batch[t] * vis;
-      T = next_T;
-      cur_idx = batch_start + t;
-    }
-  }
-  if (inside) {
-    const int pix = pi * img_w + pj;
-    final_Ts[pix] = T;
-    final_idx[pix] = cur_idx;
-    float o0 = c0 + T * background[0], o1 = c1 + T * background[1], o2 = c2 + T * background[2];
-    if (clamp_max1) {
-      o0 = fminf(o0, 1.f); o1 = fminf(o1, 1.f); o2 = fminf(o2, 1.f);
-    }
-    out_img[3 * pix + 0] = o0;
-    out_img[3 * pix + 1] = o1;
-    out_img[3 * pix + 2] = o2;
-    if (out_alpha) out_alpha[pix] = 1.f - T;
-  }
-}
-
-// ---- exact contribution culling (eval path, ABI v9) ---------------------------------------------------------
-// gsplat bins a Gaussian into every tile of its 3-sigma square (get_tile_bbox) and the per-pixel loop then skips
-// it wherever alpha = min(0.999, o exp(-sigma)) < 1/255.  A (Gaussian, pixel box) pair can be dropped without
-// changing any output bit when no pixel centre in the box can pass that test: sigma is a positive-definite
-// quadratic in d = (x, y) - pixel, so its minimum over the box of d is 0 (centre inside) or on an edge (a 1-D
-// quadratic clamped to the edge).  The minimum is evaluated in fp32 and compared against a limit raised by
-// margins far above every rounding involved: the kernel's own fp32 sigma (relative error <= a few ulp *
-// (1 + rho) / (1 - rho), rho = |b| / sqrt(ac) <= 0.99 here), this evaluation, __expf / __logf (absolute 1e-4 on
-// the log threshold).  Near-degenerate (rho > 0.99), non-PD and non-finite conics or positions are never
-// dropped.  Dropped pairs are exactly ones the rasterizer would `continue` past for every pixel of the box, so
-// images, alphas and final T are bit-identical; only final_idx (a list position) refers to the shorter list.
-struct CullG {
-  float gx, gy, a, b, c, ia, ic, lim;  // lim: box minimum of sigma above which the box is dropped
-  bool never, always;                  // never: o < 1/255 everywhere; always: never drop (degenerate input)
-};
-
-__device__ __forceinline__ CullG cull_setup(float x, float y, float ca, float cb, float cc, float opac) {
-  // no contraction here or in cull_box_may_hit: the count and emit kernels must take the same decision for every
-  // (Gaussian, tile) (the emit walk fills exactly the slots the count reserved), whatever FMAs the compiler
-  // would pick in each inlined copy
-#pragma clang fp contract(off)
-  CullG g;
-  g.gx = x; g.gy = y; g.a = ca; g.b = cb; g.c = cc;
-  g.ia = 0.f; g.ic = 0.f; g.lim = 0.f;
-  g.always = false; g.never = false;
-  const float ac = ca * cc;
-  if (!(ca > 0.f) || !(cc > 0.f) || !(cb * cb < 0.9801f * ac) || !isfinite(x) || !isfinite(y) || !isfinite(ac)) {
-    g.always = true;  // rho > 0.99, not positive definite, or non-finite
-    return g;
-  }
-  if (!(opac * 255.f >= 0.999f)) {  // o < 1/255 (minus 1e-3): alpha < 1/255 at every pixel; NaN: keep
-    if (opac * 255.f < 0.999f) g.never = true; else g.always = true;
-    return g;
-  }
-  const float rho = sqrtf(cb * cb / ac);
-  g.ia = 1.f / ca;
-  g.ic = 1.f / cc;
-  // may contribute iff sigma_min * (1 - 1e-4 / (1 - rho)) <= ln(255 o) + 2e-4
-  g.lim = (__logf(opac * 255.f) + 2e-4f) / (1.f - 1e-4f / (1.f - rho));
-  return g;
-}
-
-// May the Gaussian reach alpha >= 1/255 at a pixel centre of [px0, px1] x [py0, py1] (integer pixel bounds,
-// inclusive, already clipped to the image)?
-__device__ __forceinline__ bool cull_box_may_hit(const CullG& g, int px0, int px1, int py0, int py1) {
-#pragma clang fp contract(off)
-  if (g.always) return true;
-  if (g.never || px0 > px1 || py0 > py1) return false;
-  // d = g - (p + 0.5) over the pixel centres
-  const float u0 = g.gx - ((float)px1 + 0.5f), u1 = g.gx - ((float)px0 + 0.5f);
-  const float v0 = g.gy - ((float)py1 + 0.5f), v1 = g.gy - ((float)py0 + 0.5f);
-  if (u0 <= 0.f && u1 >= 0.f && v0 <= 0.f && v1 >= 0.f) return true;
-  float m = 3.0e38f;
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const float dx = e ? u1 : u0;
-    const float dy = fminf(fmaxf(-g.b * dx * g.ic, v0), v1);
-    m = fminf(m, 0.5f * (g.a * dx * dx + g.c * dy * dy) + g.b * dx * dy);
-    const float ey = e ? v1 : v0;
-    const float ex = fminf(fmaxf(-g.b * ey * g.ia, u0), u1);
-    m = fminf(m, 0.5f * (g.a * ex * ex + g.c * ey * ey) + g.b * ex * ey);
-  }
-  return m <= g.lim;
-}
-
 // Tiles of a Gaussian's gsplat square are visited in gsplat's order (row-major over the square).  Squares of up
 // to SMALL_AREA tiles are walked by their own lane; bigger ones (a few needles and near-camera Gaussians can
 // cover thousands of tiles) by the whole wave, 64 tiles per step, so no lane serialises a long walk.
@@ -1220,444 +966,6 @@ __global__ void __launch_bounds__(256) depth_keys_kernel(long long n, const floa
   if (i < n) keys[i] = (uint64_t)(unsigned)__float_as_int(depths[i]);
 }
 
-// rasterize_fwd_packed_kernel with per-wave Gaussian lists: the 16x16 tile is split into four 8x8 quadrants, one
-// per wave; while a batch is staged each lane tests its record against the four quadrants (cull_box_may_hit)
-// and every wave compacts the batch to the records that can reach its quadrant.  Each pixel still visits its
-// tile's Gaussians in list order and runs the identical arithmetic; it only skips records whose alpha is below
-// 1/255 at all of its quadrant's pixel centres -- the ones the per-pixel test would `continue` past -- so every
-// output is bit-identical to rasterize_fwd_packed_kernel over the same list.  bw must be 16.
-__global__ void __launch_bounds__(MAX_BLOCK)
-rasterize_fwd_quad_kernel(int tiles_x, int tiles_y, int img_h, int img_w, const int32_t* __restrict__ gids_sorted,
-                          const int* __restrict__ tile_bins, const float4* __restrict__ rec,
-                          const float* __restrict__ background, float* __restrict__ final_Ts,
-                          int* __restrict__ final_idx, float* __restrict__ out_img, float* __restrict__ out_alpha,
-                          int clamp_max1) {
-  // the per-pixel arithmetic spelled out with the exact contractions the compiler gives
-  // rasterize_fwd_packed_kernel / rasterize_fwd_kernel (their ISA: sigma = fma(dy, qx dx, 0.5 fma(dx, aw dx,
-  // dy (qy dy))), colour += vis c as fma, out = fma(T, bg, colour)), so the outputs match them bit for bit
-#pragma clang fp contract(off)
-  constexpr int BW = 16, BS = BW * BW;
-  __shared__ float4 r0_batch[BS];
-  __shared__ float4 r1_batch[BS];
-  __shared__ float r2_batch[BS];
-  __shared__ unsigned char mask_batch[BS];
-  __shared__ unsigned char wlist[4][BS];
-
-  const int tile_id = blockIdx.z * tiles_x * tiles_y + blockIdx.y * tiles_x + blockIdx.x;
-  if (blockIdx.z > 0) {
-    const long long po = (long long)blockIdx.z * img_h * img_w;
-    final_Ts += po; final_idx += po; out_img += 3 * po;
-    if (out_alpha) out_alpha += po;
-  }
-  const int tr = threadIdx.x;
-  const int lane = tr & 63, w = tr >> 6;
-  const int qx = (w & 1) * 8, qy = (w >> 1) * 8;
-  const unsigned pi = blockIdx.y * BW + qy + (lane >> 3), pj = blockIdx.x * BW + qx + (lane & 7);
-  const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
-  const bool inside = (pi < (unsigned)img_h && pj < (unsigned)img_w);
-  bool done = !inside;
-  // quadrant pixel boxes (clipped to the image) for the mask test
-  const int tx0 = blockIdx.x * BW, ty0 = blockIdx.y * BW;
-
-  const int range_x = tile_bins[2 * tile_id], range_y = tile_bins[2 * tile_id + 1];
-  const int num_batches = (range_y - range_x + BS - 1) / BS;
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-
-  float T = 1.f;
-  int cur_idx = 0;
-  float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-  for (int b = 0; b < num_batches; ++b) {
-    if (__syncthreads_count(done) >= BS) break;
-    const int batch_start = range_x + BS * b;
-    const int idx = batch_start + tr;
-    unsigned m = 0;
-    if (idx < range_y) {
-      const long long g = gids_sorted[idx];
-      const float4 a = rec[4 * g];
-      const float4 q = rec[4 * g + 1];
-      r0_batch[tr] = a;
-      r1_batch[tr] = q;
-      r2_batch[tr] = reinterpret_cast<const float*>(rec + 4 * g + 2)[0];
-      const CullG cg = cull_setup(a.x, a.y, a.w, q.x, q.y, a.z);
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int bx0 = tx0 + (qd & 1) * 8, by0 = ty0 + (qd >> 1) * 8;
-        m |= (unsigned)cull_box_may_hit(cg, bx0, min(bx0 + 8, img_w) - 1, by0, min(by0 + 8, img_h) - 1) << qd;
-      }
-    }
-    mask_batch[tr] = (unsigned char)m;
-    __syncthreads();
-    // this wave's list: batch positions whose record may reach the quadrant, in batch order
-    int cnt = 0;
-#pragma unroll
-    for (int ch = 0; ch < BS / 64; ++ch) {
-      const bool hit = (mask_batch[ch * 64 + lane] >> w) & 1;
-      const unsigned long long bal = __ballot(hit);
-      if (hit) wlist[w][cnt + __popcll(bal & lt_mask)] = (unsigned char)(ch * 64 + lane);
-      cnt += __popcll(bal);
-    }
-    __syncthreads();
-    for (int j = 0; (j < cnt) && !done; ++j) {
-      const int t = wlist[w][j];
-      const float4 a = r0_batch[t];
-      const float4 q = r1_batch[t];
-      const float dx = a.x - px, dy = a.y - py;
-      const float sigma = __builtin_fmaf(dy, q.x * dx, 0.5f * __builtin_fmaf(dx, a.w * dx, dy * (q.y * dy)));
-      const float alpha = fminf(0.999f, a.z * __expf(-sigma));
-      if (sigma < 0.f || alpha < 1.f / 255.f) continue;
-      const float next_T = T * (1.f - alpha);
-      if (next_T <= 1e-4f) {
-        done = true;
-        break;
-      }
-      const float vis = alpha * T;
-      c0 = __builtin_fmaf(vis, q.z, c0);
-      c1 = __builtin_fmaf(vis, q.w, c1);
-      c2 = __builtin_fmaf(vis, r2_batch[t], c2);
-      T = next_T;
-      cur_idx = batch_start + t;
-    }
-  }
-  if (inside) {
-    const int pix = pi * img_w + pj;
-    final_Ts[pix] = T;
-    final_idx[pix] = cur_idx;
-    float o0 = __builtin_fmaf(T, background[0], c0), o1 = __builtin_fmaf(T, background[1], c1),
-          o2 = __builtin_fmaf(T, background[2], c2);
-    if (clamp_max1) {
-      o0 = fminf(o0, 1.f); o1 = fminf(o1, 1.f); o2 = fminf(o2, 1.f);
-    }
-    out_img[3 * pix + 0] = o0;
-    out_img[3 * pix + 1] = o1;
-    out_img[3 * pix + 2] = o2;
-    if (out_alpha) out_alpha[pix] = 1.f - T;
-  }
-}
-
-// ---- rasterize backward -----------------------------------------------------
-__global__ void __launch_bounds__(MAX_BLOCK)
-rasterize_bwd_kernel(int tiles_x, int tiles_y, int bw, int img_h, int img_w,
-                     const int32_t* __restrict__ gids_sorted, const int* __restrict__ tile_bins,
-                     const float* __restrict__ xys, const float* __restrict__ conics,
-                     const float* __restrict__ colors, const float* __restrict__ opacity,
-                     const float* __restrict__ background, const float* __restrict__ final_Ts,
-                     const int* __restrict__ final_idx, const float* __restrict__ v_out,
-                     const float* __restrict__ v_out_alpha, float* __restrict__ v_xy,
-                     float* __restrict__ v_xy_abs, float* __restrict__ v_conic, float* __restrict__ v_rgb,
-                     float* __restrict__ v_opacity) {
-  __shared__ int id_batch[MAX_BLOCK];
-  __shared__ float4 xyo_batch[MAX_BLOCK];
-  __shared__ float4 conic_batch[MAX_BLOCK];
-  __shared__ float4 rgb_batch[MAX_BLOCK];
-
-  const int tile_id = blockIdx.y * tiles_x + blockIdx.x;
-  const int tr = threadIdx.x;
-  const int ty = tr / bw, tx = tr - (tr / bw) * bw;
-  const int block_size = bw * bw;
-  const unsigned pi = blockIdx.y * bw + ty, pj = blockIdx.x * bw + tx;
-  const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
-  const bool inside = (pi < (unsigned)img_h && pj < (unsigned)img_w);
-  const int pix = min((int)(pi * img_w + pj), img_w * img_h - 1);
-
-  const float T_final = final_Ts[pix];
-  float T = T_final;
-  float buf0 = 0.f, buf1 = 0.f, buf2 = 0.f;
-  const int bin_final = inside ? final_idx[pix] : 0;
-  const int range_x = tile_bins[2 * tile_id], range_y = tile_bins[2 * tile_id + 1];
-  const int num_batches = (range_y - range_x + block_size - 1) / block_size;
-  const float vo0 = v_out[3 * pix], vo1 = v_out[3 * pix + 1], vo2 = v_out[3 * pix + 2];
-  const float voa = v_out_alpha ? v_out_alpha[pix] : 0.f;
-  const float bg0 = background[0], bg1 = background[1], bg2 = background[2];
-  const int wave_bin_final = sfx::wave_max_i(bin_final);
-  const int lane = threadIdx.x & 63;
-
-  for (int b = 0; b < num_batches; ++b) {
-    __syncthreads();
-    const int batch_end = range_y - 1 - block_size * b;
-    const int batch_size = min(block_size, batch_end + 1 - range_x);
-    const int idx = batch_end - tr;
-    if (idx >= range_x) {
-      const int g = gids_sorted[idx];
-      id_batch[tr] = g;
-      xyo_batch[tr] = make_float4(xys[2 * g], xys[2 * g + 1], opacity[g], 0.f);
-      conic_batch[tr] = make_float4(conics[3 * g], conics[3 * g + 1], conics[3 * g + 2], 0.f);
-      rgb_batch[tr] = make_float4(colors[3 * g], colors[3 * g + 1], colors[3 * g + 2], 0.f);
-    }
-    __syncthreads();
-    for (int t = max(0, batch_end - wave_bin_final); t < batch_size; ++t) {
-      bool valid = inside && (batch_end - t <= bin_final);
-      float alpha = 0.f, opac = 0.f, vis = 0.f, dx = 0.f, dy = 0.f;
-      float4 con = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (valid) {
-        con = conic_batch[t];
-        const float4 xyo = xyo_batch[t];
-        opac = xyo.z;
-        dx = xyo.x - px;
-        dy = xyo.y - py;
-        const float sigma = 0.5f * (con.x * dx * dx + con.z * dy * dy) + con.y * dx * dy;
-        vis = __expf(-sigma);
-        alpha = fminf(0.99f, opac * vis);
-        if (sigma < 0.f || alpha < 1.f / 255.f) valid = false;
-      }
-      if (!__any(valid)) continue;
-      float g_rgb0 = 0.f, g_rgb1 = 0.f, g_rgb2 = 0.f, g_c0 = 0.f, g_c1 = 0.f, g_c2 = 0.f;
-      float g_xy0 = 0.f, g_xy1 = 0.f, g_ax = 0.f, g_ay = 0.f, g_o = 0.f;
-      if (valid) {
-        const float ra = 1.f / (1.f - alpha);
-        T *= ra;
-        const float fac = alpha * T;
-        g_rgb0 = fac * vo0;
-        g_rgb1 = fac * vo1;
-        g_rgb2 = fac * vo2;
-        const float4 rgb = rgb_batch[t];
-        float v_alpha = 0.f;
-        v_alpha += (rgb.x * T - buf0 * ra) * vo0;
-        v_alpha += (rgb.y * T - buf1 * ra) * vo1;
-        v_alpha += (rgb.z * T - buf2 * ra) * vo2;
-        v_alpha += T_final * ra * voa;
-        v_alpha += -T_final * ra * bg0 * vo0;
-        v_alpha += -T_final * ra * bg1 * vo1;
-        v_alpha += -T_final * ra * bg2 * vo2;
-        buf0 += rgb.x * fac;
-        buf1 += rgb.y * fac;
-        buf2 += rgb.z * fac;
-        const float v_sigma = -opac * vis * v_alpha;
-        g_c0 = 0.5f * v_sigma * dx * dx;
-        g_c1 = v_sigma * dx * dy;
-        g_c2 = 0.5f * v_sigma * dy * dy;
-        g_xy0 = v_sigma * (con.x * dx + con.y * dy);
-        g_xy1 = v_sigma * (con.y * dx + con.z * dy);
-        g_ax = fabsf(g_xy0);
-        g_ay = fabsf(g_xy1);
-        g_o = vis * v_alpha;
-      }
-      g_rgb0 = sfx::wave_sum_dpp(g_rgb0);
-      g_rgb1 = sfx::wave_sum_dpp(g_rgb1);
-      g_rgb2 = sfx::wave_sum_dpp(g_rgb2);
-      g_c0 = sfx::wave_sum_dpp(g_c0);
-      g_c1 = sfx::wave_sum_dpp(g_c1);
-      g_c2 = sfx::wave_sum_dpp(g_c2);
-      g_xy0 = sfx::wave_sum_dpp(g_xy0);
-      g_xy1 = sfx::wave_sum_dpp(g_xy1);
-      g_o = sfx::wave_sum_dpp(g_o);
-      if (v_xy_abs) {
-        g_ax = sfx::wave_sum_dpp(g_ax);
-        g_ay = sfx::wave_sum_dpp(g_ay);
-      }
-      if (lane == 0) {
-        const int g = id_batch[t];
-        atomicAdd(v_rgb + 3 * g + 0, g_rgb0);
-        atomicAdd(v_rgb + 3 * g + 1, g_rgb1);
-        atomicAdd(v_rgb + 3 * g + 2, g_rgb2);
-        atomicAdd(v_conic + 3 * g + 0, g_c0);
-        atomicAdd(v_conic + 3 * g + 1, g_c1);
-        atomicAdd(v_conic + 3 * g + 2, g_c2);
-        atomicAdd(v_xy + 2 * g + 0, g_xy0);
-        atomicAdd(v_xy + 2 * g + 1, g_xy1);
-        if (v_xy_abs) {
-          atomicAdd(v_xy_abs + 2 * g + 0, g_ax);
-          atomicAdd(v_xy_abs + 2 * g + 1, g_ay);
-        }
-        atomicAdd(v_opacity + g, g_o);
-      }
-    }
-  }
-}
-
-// rasterize_bwd_kernel over a culled list with rasterize_fwd_quad_kernel's layout: one 8x8 quadrant per wave
-// and, per batch, per-wave lists of the records that can reach the quadrant (cull_box_may_hit) and lie at or
-// before the wave's last contributing position (final_idx).  Every skipped record has alpha < 1/255 at each
-// pixel of the quadrant -- the per-pixel `valid` test would be false for all lanes -- so each pixel sees the same
-// contributions in the same back-to-front order; per-Gaussian sums per wave as before (one atomic per wave and
-// Gaussian that any lane of the wave touches).  bw = 16.
-__global__ void __launch_bounds__(MAX_BLOCK)
-rasterize_bwd_quad_kernel(int tiles_x, int tiles_y, int img_h, int img_w, const int32_t* __restrict__ gids_sorted,
-                          const int* __restrict__ tile_bins, const float* __restrict__ xys,
-                          const float* __restrict__ conics, const float* __restrict__ colors,
-                          const float* __restrict__ opacity, const float* __restrict__ background,
-                          const float* __restrict__ final_Ts, const int* __restrict__ final_idx,
-                          const float* __restrict__ v_out, const float* __restrict__ v_out_alpha,
-                          float* __restrict__ v_xy, float* __restrict__ v_xy_abs, float* __restrict__ v_conic,
-                          float* __restrict__ v_rgb, float* __restrict__ v_opacity) {
-  constexpr int BW = 16, BS = BW * BW;
-  __shared__ int id_batch[BS];
-  __shared__ float4 xyo_batch[BS];
-  __shared__ float4 conic_batch[BS];
-  __shared__ float4 rgb_batch[BS];
-  __shared__ unsigned char mask_batch[BS];
-  __shared__ unsigned char wlist[4][BS];
-
-  // batched views (sfx_rasterize_bwd_views_quad): blockIdx.z = view, as rasterize_fwd_quad_kernel -- tiles numbered
-  // per view, per-view image planes; gids_sorted / final_idx index the one multi-view list, the per-Gaussian
-  // operands and gradients are per Gaussian-view
-  const int tile_id = blockIdx.z * tiles_x * tiles_y + blockIdx.y * tiles_x + blockIdx.x;
-  if (blockIdx.z > 0) {
-    const long long po = (long long)blockIdx.z * img_h * img_w;
-    final_Ts += po; final_idx += po; v_out += 3 * po;
-    if (v_out_alpha) v_out_alpha += po;
-  }
-  const int tr = threadIdx.x;
-  const int lane = tr & 63, w = tr >> 6;
-  const int qx = (w & 1) * 8, qy = (w >> 1) * 8;
-  const unsigned pi = blockIdx.y * BW + qy + (lane >> 3), pj = blockIdx.x * BW + qx + (lane & 7);
-  const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
-  const bool inside = (pi < (unsigned)img_h && pj < (unsigned)img_w);
-  const int pix = min((int)(pi * img_w + pj), img_w * img_h - 1);
-  const int tx0 = blockIdx.x * BW, ty0 = blockIdx.y * BW;
-
-  const float T_final = final_Ts[pix];
-  float T = T_final;
-  float buf0 = 0.f, buf1 = 0.f, buf2 = 0.f;
-  const int bin_final = inside ? final_idx[pix] : 0;
-  const int range_x = tile_bins[2 * tile_id], range_y = tile_bins[2 * tile_id + 1];
-  const int num_batches = (range_y - range_x + BS - 1) / BS;
-  const float vo0 = v_out[3 * pix], vo1 = v_out[3 * pix + 1], vo2 = v_out[3 * pix + 2];
-  const float voa = v_out_alpha ? v_out_alpha[pix] : 0.f;
-  const float bg0 = background[0], bg1 = background[1], bg2 = background[2];
-  const int wave_bin_final = sfx::wave_max_i(inside ? bin_final : -1);
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  constexpr int RING = 8;
-  __shared__ float ring[4][RING][12][4];
-  __shared__ int ring_g[4][RING];
-  int nring = 0;  // records parked in this wave's ring (wave-uniform)
-  auto flush_ring = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int nv = v_xy_abs ? 11 : 9;
-    for (int e = lane; e < nring * nv; e += 64) {
-      const int jj = e / nv, c = e - jj * nv;
-      const float* q = ring[w][jj][c];
-      const float sum = (q[0] + q[1]) + (q[2] + q[3]);
-      const int g = ring_g[w][jj];
-      float* dst = c < 3 ? v_rgb + 3 * g + c
-                 : c < 6 ? v_conic + 3 * g + (c - 3)
-                 : c < 8 ? v_xy + 2 * g + (c - 6)
-                 : c == 8 ? v_opacity + g
-                          : v_xy_abs + 2 * g + (c - 9);
-      atomicAdd(dst, sum);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    nring = 0;
-  };
-
-  for (int b = 0; b < num_batches; ++b) {
-    __syncthreads();
-    const int batch_end = range_y - 1 - BS * b;
-    const int idx = batch_end - tr;
-    unsigned m = 0;
-    if (idx >= range_x) {
-      const int g = gids_sorted[idx];
-      const float4 xyo = make_float4(xys[2 * g], xys[2 * g + 1], opacity[g], 0.f);
-      const float4 con = make_float4(conics[3 * g], conics[3 * g + 1], conics[3 * g + 2], 0.f);
-      id_batch[tr] = g;
-      xyo_batch[tr] = xyo;
-      conic_batch[tr] = con;
-      rgb_batch[tr] = make_float4(colors[3 * g], colors[3 * g + 1], colors[3 * g + 2], 0.f);
-      const CullG cg = cull_setup(xyo.x, xyo.y, con.x, con.y, con.z, xyo.z);
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int bx0 = tx0 + (qd & 1) * 8, by0 = ty0 + (qd >> 1) * 8;
-        m |= (unsigned)cull_box_may_hit(cg, bx0, min(bx0 + 8, img_w) - 1, by0, min(by0 + 8, img_h) - 1) << qd;
-      }
-    }
-    mask_batch[tr] = (unsigned char)m;
-    __syncthreads();
-    int cnt = 0;
-#pragma unroll
-    for (int ch = 0; ch < BS / 64; ++ch) {
-      const int t = ch * 64 + lane;
-      const bool hit = ((mask_batch[t] >> w) & 1) && (batch_end - t <= wave_bin_final);
-      const unsigned long long bal = __ballot(hit);
-      if (hit) wlist[w][cnt + __popcll(bal & lt_mask)] = (unsigned char)t;
-      cnt += __popcll(bal);
-    }
-    __syncthreads();
-    for (int j = 0; j < cnt; ++j) {
-      const int t = wlist[w][j];
-      bool valid = inside && (batch_end - t <= bin_final);
-      float alpha = 0.f, opac = 0.f, vis = 0.f, dx = 0.f, dy = 0.f;
-      float4 con = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (valid) {
-        con = conic_batch[t];
-        const float4 xyo = xyo_batch[t];
-        opac = xyo.z;
-        dx = xyo.x - px;
-        dy = xyo.y - py;
-        const float sigma = 0.5f * (con.x * dx * dx + con.z * dy * dy) + con.y * dx * dy;
-        vis = __expf(-sigma);
-        alpha = fminf(0.99f, opac * vis);
-        if (sigma < 0.f || alpha < 1.f / 255.f) valid = false;
-      }
-      if (!__any(valid)) continue;
-      float g_rgb0 = 0.f, g_rgb1 = 0.f, g_rgb2 = 0.f, g_c0 = 0.f, g_c1 = 0.f, g_c2 = 0.f;
-      float g_xy0 = 0.f, g_xy1 = 0.f, g_ax = 0.f, g_ay = 0.f, g_o = 0.f;
-      if (valid) {
-        const float ra = 1.f / (1.f - alpha);
-        T *= ra;
-        const float fac = alpha * T;
-        g_rgb0 = fac * vo0;
-        g_rgb1 = fac * vo1;
-        g_rgb2 = fac * vo2;
-        const float4 rgb = rgb_batch[t];
-        float v_alpha = 0.f;
-        v_alpha += (rgb.x * T - buf0 * ra) * vo0;
-        v_alpha += (rgb.y * T - buf1 * ra) * vo1;
-        v_alpha += (rgb.z * T - buf2 * ra) * vo2;
-        v_alpha += T_final * ra * voa;
-        v_alpha += -T_final * ra * bg0 * vo0;
-        v_alpha += -T_final * ra * bg1 * vo1;
-        v_alpha += -T_final * ra * bg2 * vo2;
-        buf0 += rgb.x * fac;
-        buf1 += rgb.y * fac;
-        buf2 += rgb.z * fac;
-        const float v_sigma = -opac * vis * v_alpha;
-        g_c0 = 0.5f * v_sigma * dx * dx;
-        g_c1 = v_sigma * dx * dy;
-        g_c2 = 0.5f * v_sigma * dy * dy;
-        g_xy0 = v_sigma * (con.x * dx + con.y * dy);
-        g_xy1 = v_sigma * (con.y * dx + con.z * dy);
-        g_ax = fabsf(g_xy0);
-        g_ay = fabsf(g_xy1);
-        g_o = vis * v_alpha;
-      }
-      // row sums of the 12 slots by a transposing butterfly: lane bit 0 then bit 1 split the slots between the
-      // two partners (each keeps half, adds the other's copy of it: 12 -> 6 -> 3 slots per lane), then two
-      // rotations sum the row's 4 quads -- 6 + 3 + 6 DPP moves instead of 4 per slot.  Lane (l & 3) of each row
-      // then holds slots 6 (l & 1) + 3 ((l >> 1) & 1) + {0, 1, 2}, parked in this wave's LDS ring; the 4 row
-      // partials of 8 records are added and sent with one atomic per (record, value) by the wave's lanes in
-      // parallel (flush below)
-      const float vals[12] = {g_rgb0, g_rgb1, g_rgb2, g_c0, g_c1, g_c2, g_xy0, g_xy1, g_o, g_ax, g_ay, 0.f};
-      const bool hi0 = lane & 1, hi1 = lane & 2;
-      float h6[6], h3[3];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const float keep = hi0 ? vals[i + 6] : vals[i], send = hi0 ? vals[i] : vals[i + 6];
-        h6[i] = keep + sfx::dpp_mov<0xB1>(send);  // quad [1,0,3,2]
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const float keep = hi1 ? h6[i + 3] : h6[i], send = hi1 ? h6[i] : h6[i + 3];
-        h3[i] = keep + sfx::dpp_mov<0x4E>(send);  // quad [2,3,0,1]
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i) h3[i] += sfx::dpp_mov<0x124>(h3[i]);  // row_ror:4
-#pragma unroll
-      for (int i = 0; i < 3; ++i) h3[i] += sfx::dpp_mov<0x128>(h3[i]);  // row_ror:8
-      if ((lane & 15) < 4) {
-        const int base = 6 * (lane & 1) + 3 * ((lane >> 1) & 1);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) ring[w][nring][base + i][lane >> 4] = h3[i];
-      }
-      if (lane == 0) ring_g[w][nring] = id_batch[t];
-      if (++nring == RING) flush_ring();
-    }
-  }
-  flush_ring();
-}
-
 }  // namespace
 
 extern "C" {
@@ -1767,40 +1075,6 @@ int sfx_tile_bins(int num_isect, const int64_t* isect_ids_sorted, int num_tiles,
   return sfx::check_launch("sfx_tile_bins");
 }
 
-int sfx_rasterize_fwd(int tiles_x, int tiles_y, int block_width, int img_h, int img_w, const int32_t* gids_sorted,
-                      const int* tile_bins, const float* xys, const float* conics, const float* colors,
-                      const float* opacity, const float* background, float* final_Ts, int* final_idx,
-                      float* out_img, float* out_alpha, void* stream) {
-  SFX_REQUIRE(block_width > 1 && block_width <= 16, "sfx_rasterize_fwd: block_width must be in (1,16]");
-  SFX_REQUIRE(tiles_x == (img_w + block_width - 1) / block_width && tiles_y == (img_h + block_width - 1) / block_width,
-              "sfx_rasterize_fwd: tile bounds do not match the image size");
-  SFX_REQUIRE(tile_bins && xys && conics && colors && opacity && background && final_Ts && final_idx && out_img,
-              "sfx_rasterize_fwd: null buffer");
-  dim3 grid(tiles_x, tiles_y);
-  rasterize_fwd_kernel<<<grid, block_width * block_width, 0, sfx::as_stream(stream)>>>(
-      tiles_x, tiles_y, block_width, img_h, img_w, gids_sorted, tile_bins, xys, conics, colors, opacity, background,
-      final_Ts, final_idx, out_img, out_alpha, 0);
-  return sfx::check_launch("sfx_rasterize_fwd");
-}
-
-int sfx_rasterize_bwd(int tiles_x, int tiles_y, int block_width, int img_h, int img_w, const int32_t* gids_sorted,
-                      const int* tile_bins, const float* xys, const float* conics, const float* colors,
-                      const float* opacity, const float* background, const float* final_Ts, const int* final_idx,
-                      const float* v_out, const float* v_out_alpha, float* v_xy, float* v_xy_abs, float* v_conic,
-                      float* v_rgb, float* v_opacity, void* stream) {
-  SFX_REQUIRE(block_width > 1 && block_width <= 16, "sfx_rasterize_bwd: block_width must be in (1,16]");
-  SFX_REQUIRE(tiles_x == (img_w + block_width - 1) / block_width && tiles_y == (img_h + block_width - 1) / block_width,
-              "sfx_rasterize_bwd: tile bounds do not match the image size");
-  SFX_REQUIRE(tile_bins && xys && conics && colors && opacity && background && final_Ts && final_idx && v_out &&
-                  v_xy && v_conic && v_rgb && v_opacity,
-              "sfx_rasterize_bwd: null buffer");
-  dim3 grid(tiles_x, tiles_y);
-  rasterize_bwd_kernel<<<grid, block_width * block_width, 0, sfx::as_stream(stream)>>>(
-      tiles_x, tiles_y, block_width, img_h, img_w, gids_sorted, tile_bins, xys, conics, colors, opacity, background,
-      final_Ts, final_idx, v_out, v_out_alpha, v_xy, v_xy_abs, v_conic, v_rgb, v_opacity);
-  return sfx::check_launch("sfx_rasterize_bwd");
-}
-
 // ---- batched views (eval path of rasterize_gaussians_to_multiimgs) --------------------------------------
 // All V cameras share the intrinsics / image size (the reference's cameras dict); per-view records are laid
 // out view-major ([V, n, ...]); intersections of all views are sorted once (tile ids offset by view * T).
@@ -1844,59 +1118,11 @@ int sfx_isect_emit_views(int n_total, int n_per_view, const float* xys, const fl
   return sfx::check_launch("sfx_isect_emit_views");
 }
 
-int sfx_rasterize_fwd_views(int views, int tiles_x, int tiles_y, int block_width, int img_h, int img_w,
-                            const int32_t* gids_sorted, const int* tile_bins, const float* xys, const float* conics,
-                            const float* colors, const float* opacity, const float* background, int clamp_max1,
-                            float* final_Ts, int* final_idx, float* out_img, float* out_alpha, void* stream) {
-  SFX_REQUIRE(views >= 1 && views <= 65535, "sfx_rasterize_fwd_views: bad view count");
-  SFX_REQUIRE(block_width > 1 && block_width <= 16, "sfx_rasterize_fwd_views: block_width must be in (1,16]");
-  SFX_REQUIRE(tiles_x == (img_w + block_width - 1) / block_width && tiles_y == (img_h + block_width - 1) / block_width,
-              "sfx_rasterize_fwd_views: tile bounds do not match the image size");
-  SFX_REQUIRE(tile_bins && xys && conics && colors && opacity && background && final_Ts && final_idx && out_img,
-              "sfx_rasterize_fwd_views: null buffer");
-  dim3 grid(tiles_x, tiles_y, views);
-  rasterize_fwd_kernel<<<grid, block_width * block_width, 0, sfx::as_stream(stream)>>>(
-      tiles_x, tiles_y, block_width, img_h, img_w, gids_sorted, tile_bins, xys, conics, colors, opacity, background,
-      final_Ts, final_idx, out_img, out_alpha, clamp_max1);
-  return sfx::check_launch("sfx_rasterize_fwd_views");
-}
-
-int sfx_pack_raster_records(int n, const float* xys, const float* conics, const float* colors, const float* opacity,
-                            float* records, void* stream) {
-  SFX_REQUIRE(n >= 0, "sfx_pack_raster_records: n < 0");
-  if (n == 0) return SFX_OK;
-  SFX_REQUIRE(xys && conics && colors && opacity && records, "sfx_pack_raster_records: null buffer");
-  SFX_REQUIRE((reinterpret_cast<uintptr_t>(records) & 15) == 0, "sfx_pack_raster_records: records not 16-byte aligned");
-  pack_raster_records_kernel<<<sfx::ceil_div(n, 256), 256, 0, sfx::as_stream(stream)>>>(
-      n, xys, conics, colors, opacity, reinterpret_cast<float4*>(records));
-  return sfx::check_launch("sfx_pack_raster_records");
-}
-
-int sfx_rasterize_fwd_views_packed(int views, int tiles_x, int tiles_y, int block_width, int img_h, int img_w,
-                                   const int32_t* gids_sorted, const int* tile_bins, const float* records,
-                                   const float* background, int clamp_max1, float* final_Ts, int* final_idx,
-                                   float* out_img, float* out_alpha, void* stream) {
-  SFX_REQUIRE(views >= 1 && views <= 65535, "sfx_rasterize_fwd_views_packed: bad view count");
-  SFX_REQUIRE(block_width > 1 && block_width <= 16, "sfx_rasterize_fwd_views_packed: block_width must be in (1,16]");
-  SFX_REQUIRE(tiles_x == (img_w + block_width - 1) / block_width && tiles_y == (img_h + block_width - 1) / block_width,
-              "sfx_rasterize_fwd_views_packed: tile bounds do not match the image size");
-  SFX_REQUIRE(tile_bins && records && background && final_Ts && final_idx && out_img,
-              "sfx_rasterize_fwd_views_packed: null buffer");
-  SFX_REQUIRE((reinterpret_cast<uintptr_t>(records) & 15) == 0, "sfx_rasterize_fwd_views_packed: records alignment");
-  dim3 grid(tiles_x, tiles_y, views);
-  rasterize_fwd_packed_kernel<<<grid, block_width * block_width, 0, sfx::as_stream(stream)>>>(
-      tiles_x, tiles_y, block_width, img_h, img_w, gids_sorted, tile_bins, reinterpret_cast<const float4*>(records),
-      background, final_Ts, final_idx, out_img, out_alpha, clamp_max1);
-  return sfx::check_launch("sfx_rasterize_fwd_views_packed");
-}
-
 int sfx_isect_count_cull_views(int n_total, int n_per_view, const float* xys, const float* conics,
                                const float* opacities, const int* radii, int tiles_x, int tiles_y, int block_width,
                                int img_h, int img_w, int* num_tiles_kept, void* stream) {
   SFX_REQUIRE(n_total >= 0 && n_per_view > 0 && n_total % n_per_view == 0, "sfx_isect_count_cull_views: bad sizes");
-  SFX_REQUIRE(block_width > 1 && block_width <= 16, "sfx_isect_count_cull_views: block_width must be in (1,16]");
-  SFX_REQUIRE(tiles_x == (img_w + block_width - 1) / block_width && tiles_y == (img_h + block_width - 1) / block_width,
-              "sfx_isect_count_cull_views: tile bounds do not match the image size");
+  SFX_RASTER_CHECK("sfx_isect_count_cull_views", nullptr, tiles_x, tiles_y, block_width, img_h, img_w, false);
   if (n_total == 0) return SFX_OK;
   SFX_REQUIRE(xys && conics && opacities && radii && num_tiles_kept, "sfx_isect_count_cull_views: null buffer");
   isect_count_cull_kernel<<<sfx::ceil_div(n_total, 256), 256, 0, sfx::as_stream(stream)>>>(
@@ -1909,9 +1135,7 @@ int sfx_isect_emit_cull_views(int n_total, int n_per_view, const float* xys, con
                               int tiles_x, int tiles_y, int block_width, int img_h, int img_w, int64_t* isect_ids,
                               int32_t* gaussian_ids, const int* rank, long long capacity, void* stream) {
   SFX_REQUIRE(n_total >= 0 && n_per_view > 0 && n_total % n_per_view == 0, "sfx_isect_emit_cull_views: bad sizes");
-  SFX_REQUIRE(block_width > 1 && block_width <= 16, "sfx_isect_emit_cull_views: block_width must be in (1,16]");
-  SFX_REQUIRE(tiles_x == (img_w + block_width - 1) / block_width && tiles_y == (img_h + block_width - 1) / block_width,
-              "sfx_isect_emit_cull_views: tile bounds do not match the image size");
+  SFX_RASTER_CHECK("sfx_isect_emit_cull_views", nullptr, tiles_x, tiles_y, block_width, img_h, img_w, false);
   if (n_total == 0) return SFX_OK;
   SFX_REQUIRE(xys && conics && opacities && depths && radii && cum_tiles_hit && isect_ids && gaussian_ids,
               "sfx_isect_emit_cull_views: null buffer");
@@ -1935,63 +1159,6 @@ int sfx_depth_keys(long long n, const float* depths, uint64_t* keys, void* strea
   SFX_REQUIRE(depths && keys, "sfx_depth_keys: null buffer");
   depth_keys_kernel<<<sfx::ceil_div(n, 256), 256, 0, sfx::as_stream(stream)>>>(n, depths, keys);
   return sfx::check_launch("sfx_depth_keys");
-}
-
-int sfx_rasterize_fwd_views_quad(int views, int tiles_x, int tiles_y, int block_width, int img_h, int img_w,
-                                 const int32_t* gids_sorted, const int* tile_bins, const float* records,
-                                 const float* background, int clamp_max1, float* final_Ts, int* final_idx,
-                                 float* out_img, float* out_alpha, void* stream) {
-  SFX_REQUIRE(views >= 1 && views <= 65535, "sfx_rasterize_fwd_views_quad: bad view count");
-  SFX_REQUIRE(block_width == 16, "sfx_rasterize_fwd_views_quad: block_width must be 16");
-  SFX_REQUIRE(tiles_x == (img_w + 15) / 16 && tiles_y == (img_h + 15) / 16,
-              "sfx_rasterize_fwd_views_quad: tile bounds do not match the image size");
-  SFX_REQUIRE(tile_bins && records && background && final_Ts && final_idx && out_img,
-              "sfx_rasterize_fwd_views_quad: null buffer");
-  SFX_REQUIRE((reinterpret_cast<uintptr_t>(records) & 15) == 0, "sfx_rasterize_fwd_views_quad: records alignment");
-  dim3 grid(tiles_x, tiles_y, views);
-  rasterize_fwd_quad_kernel<<<grid, 256, 0, sfx::as_stream(stream)>>>(
-      tiles_x, tiles_y, img_h, img_w, gids_sorted, tile_bins, reinterpret_cast<const float4*>(records), background,
-      final_Ts, final_idx, out_img, out_alpha, clamp_max1);
-  return sfx::check_launch("sfx_rasterize_fwd_views_quad");
-}
-
-int sfx_rasterize_bwd_quad(int tiles_x, int tiles_y, int block_width, int img_h, int img_w, const int32_t* gids_sorted,
-                           const int* tile_bins, const float* xys, const float* conics, const float* colors,
-                           const float* opacity, const float* background, const float* final_Ts, const int* final_idx,
-                           const float* v_out, const float* v_out_alpha, float* v_xy, float* v_xy_abs, float* v_conic,
-                           float* v_rgb, float* v_opacity, void* stream) {
-  SFX_REQUIRE(block_width == 16, "sfx_rasterize_bwd_quad: block_width must be 16");
-  SFX_REQUIRE(tiles_x == (img_w + 15) / 16 && tiles_y == (img_h + 15) / 16,
-              "sfx_rasterize_bwd_quad: tile bounds do not match the image size");
-  SFX_REQUIRE(tile_bins && xys && conics && colors && opacity && background && final_Ts && final_idx && v_out &&
-                  v_xy && v_conic && v_rgb && v_opacity,
-              "sfx_rasterize_bwd_quad: null buffer");
-  dim3 grid(tiles_x, tiles_y);
-  rasterize_bwd_quad_kernel<<<grid, 256, 0, sfx::as_stream(stream)>>>(
-      tiles_x, tiles_y, img_h, img_w, gids_sorted, tile_bins, xys, conics, colors, opacity, background, final_Ts,
-      final_idx, v_out, v_out_alpha, v_xy, v_xy_abs, v_conic, v_rgb, v_opacity);
-  return sfx::check_launch("sfx_rasterize_bwd_quad");
-}
-
-// ---- batched views, backward (the training render of rasterize_gaussians_to_multiimgs_batched) --------------
-int sfx_rasterize_bwd_views_quad(int views, int tiles_x, int tiles_y, int block_width, int img_h, int img_w,
-                                 const int32_t* gids_sorted, const int* tile_bins, const float* xys,
-                                 const float* conics, const float* colors, const float* opacity,
-                                 const float* background, const float* final_Ts, const int* final_idx,
-                                 const float* v_out, const float* v_out_alpha, float* v_xy, float* v_xy_abs,
-                                 float* v_conic, float* v_rgb, float* v_opacity, void* stream) {
-  SFX_REQUIRE(views >= 1 && views <= 65535, "sfx_rasterize_bwd_views_quad: views must be in [1,65535]");
-  SFX_REQUIRE(block_width == 16, "sfx_rasterize_bwd_views_quad: block_width must be 16");
-  SFX_REQUIRE(img_h > 0 && img_w > 0 && tiles_x == (img_w + 15) / 16 && tiles_y == (img_h + 15) / 16,
-              "sfx_rasterize_bwd_views_quad: tile bounds do not match the image size");
-  SFX_REQUIRE(gids_sorted && tile_bins && xys && conics && colors && opacity && background && final_Ts && final_idx &&
-                  v_out && v_xy && v_conic && v_rgb && v_opacity,
-              "sfx_rasterize_bwd_views_quad: null buffer");
-  dim3 grid(tiles_x, tiles_y, views);
-  rasterize_bwd_quad_kernel<<<grid, 256, 0, sfx::as_stream(stream)>>>(
-      tiles_x, tiles_y, img_h, img_w, gids_sorted, tile_bins, xys, conics, colors, opacity, background, final_Ts,
-      final_idx, v_out, v_out_alpha, v_xy, v_xy_abs, v_conic, v_rgb, v_opacity);
-  return sfx::check_launch("sfx_rasterize_bwd_views_quad");
 }
 
 int sfx_render_prep_project_views_bwd(int n, int views, int num_bases, const float* means, long long ld_means,

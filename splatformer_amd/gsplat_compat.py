@@ -4,7 +4,7 @@ Same names, argument order, return tuples and autograd behaviour as
 `gsplat.spherical_harmonics`, `gsplat.project_gaussians` and
 `gsplat.rasterize_gaussians` as called from reference utils/gs_utils.py:78,
 :82-95 and :96-109.  Every op runs on the libsfx HIP kernels
-(csrc/render.hip, csrc/sort.hip); there is no CPU path.
+(csrc/render.hip, csrc/rasterize.hip, csrc/sort.hip); there is no CPU path.
 """
 from __future__ import annotations
 
@@ -32,7 +32,7 @@ def deg_from_sh(num_bases: int) -> int:
     return d[num_bases]
 
 
-# exact contribution culling (ABI v9, csrc/render.hip): the rasterizer runs over the (Gaussian, tile) pairs that
+# exact contribution culling (ABI v9, csrc/raster_common.h): the rasterizer runs over the (Gaussian, tile) pairs that
 # can reach alpha >= 1/255 -- forward outputs bit-identical, gradients the same sums in another atomic order.
 # SFX_RENDER_CULL=0 restores gsplat's full 3-sigma lists.
 CULL = os.environ.get("SFX_RENDER_CULL", "1") != "0"
@@ -158,6 +158,41 @@ def bin_and_sort_gaussians(num_points: int, num_intersects: int, xys: Tensor, de
     return isect_ids, gids, isect_sorted, gids_sorted, tile_bins
 
 
+def _raster_lists(xys, depths, radii, conics, num_tiles_hit, opacity, background, C, H, W, bw):
+    """What both rasterizer Functions do before their kernels: choose the list (culled when CULL, block_width 16 and
+    n > 0; gsplat's otherwise), read its length back (one host sync) and build it.
+    -> (num_isect, culled, gids_sorted, tile_bins, early); early = (out, alpha, final_Ts, final_idx) where no
+    kernel has to run -- gsplat's list is empty (its v0.1.11 empty-branch quirk: alpha == 1) or nothing reaches
+    1/255 anywhere -- else None."""
+    dev, n = xys.device, xys.shape[0]
+    tiles_x, tiles_y = (W + bw - 1) // bw, (H + bw - 1) // bw
+    radii = radii.to(torch.int32).contiguous()
+    culled = CULL and bw == 16 and n > 0
+    if culled:
+        # gsplat's own list only decides the empty-image branch: one device flag, read back together with the
+        # culled list's total (one host sync per view, as gsplat's num_intersects read)
+        num_isect, kept_total, kept_cum = _culled_counts(n, num_tiles_hit, xys, radii, conics, opacity, H, W, tiles_x,
+                                                         tiles_y)
+    else:
+        num_isect, cum = compute_cumulative_intersects(num_tiles_hit) if n else (0, None)
+    if num_isect < 1:
+        final_Ts = torch.zeros(H, W, device=dev)  # gsplat v0.1.11 empty-branch quirk (alpha == 1)
+        early = (torch.ones(H, W, C, device=dev) * background, 1 - final_Ts, final_Ts,
+                 torch.zeros(H, W, device=dev, dtype=torch.int32))
+        return (num_isect, culled, torch.zeros(0, device=dev, dtype=torch.int32),
+                torch.zeros(0, 2, device=dev, dtype=torch.int32), early)
+    if culled and kept_total < 1:
+        *early, gids_sorted, tile_bins = _all_culled(background, H, W, tiles_x, tiles_y)
+        return num_isect, culled, gids_sorted, tile_bins, tuple(early)
+    if culled:
+        gids_sorted, tile_bins = _culled_list(n, xys, _f32(depths), radii, conics, opacity, H, W, tiles_x, tiles_y,
+                                              kept_total, kept_cum)
+    else:
+        _, _, _, gids_sorted, tile_bins = bin_and_sort_gaussians(n, num_isect, xys, _f32(depths), radii, cum,
+                                                                 (tiles_x, tiles_y, 1), bw)
+    return num_isect, culled, gids_sorted, tile_bins, None
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height, img_width,
@@ -168,39 +203,25 @@ class _RasterizeGaussians(torch.autograd.Function):
         H, W, bw = int(img_height), int(img_width), int(block_width)
         tiles_x, tiles_y = (W + bw - 1) // bw, (H + bw - 1) // bw
         xys, conics, colors, opacity, background = map(_f32, (xys, conics, colors, opacity, background))
-        culled = CULL and bw == 16 and n > 0
-        if culled:
-            # gsplat's own list only decides the empty-image branch: one device flag, read back together with the
-            # culled list's total (one host sync per view, as gsplat's num_intersects read)
-            num_isect, kept_total, kept_cum = _culled_counts(n, num_tiles_hit, xys, radii.to(torch.int32).contiguous(),
-                                                             conics, opacity, H, W, tiles_x, tiles_y)
+        ctx.num_isect, culled, gids_sorted, tile_bins, early = _raster_lists(
+            xys, depths, radii, conics, num_tiles_hit, opacity, background, 3, H, W, bw)
+        if early is not None:
+            out, alpha, final_Ts, final_idx = early
         else:
-            num_isect, cum = compute_cumulative_intersects(num_tiles_hit) if n else (0, None)
-        ctx.num_isect = num_isect
-        if num_isect < 1:
-            out = torch.ones(H, W, colors.shape[-1], device=dev) * background
-            gids_sorted = torch.zeros(0, device=dev, dtype=torch.int32)
-            tile_bins = torch.zeros(0, 2, device=dev, dtype=torch.int32)
-            final_Ts = torch.zeros(H, W, device=dev)  # gsplat v0.1.11 empty-branch quirk (alpha == 1)
-            final_idx = torch.zeros(H, W, device=dev, dtype=torch.int32)
-            alpha = 1 - final_Ts
-        elif culled:
-            out, alpha, final_Ts, final_idx, gids_sorted, tile_bins = _culled_forward(
-                n, xys, _f32(depths), radii.to(torch.int32).contiguous(), conics, colors, opacity, background, H, W,
-                tiles_x, tiles_y, kept_total, kept_cum)
-            ctx.quad = True
-        else:
-            _, _, _, gids_sorted, tile_bins = bin_and_sort_gaussians(
-                n, num_isect, _f32(xys), _f32(depths), radii.to(torch.int32).contiguous(), cum,
-                (tiles_x, tiles_y, 1), bw)
             out = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
             final_Ts = torch.empty(H, W, device=dev, dtype=torch.float32)
             final_idx = torch.empty(H, W, device=dev, dtype=torch.int32)
             alpha = torch.empty(H, W, device=dev, dtype=torch.float32)
-            call("sfx_rasterize_fwd", tiles_x, tiles_y, bw, H, W, ptr(gids_sorted), ptr(tile_bins), ptr(xys),
-                 ptr(conics), ptr(colors), ptr(opacity), ptr(background), ptr(final_Ts), ptr(final_idx), ptr(out),
-                 ptr(alpha), stream())
-        ctx.quad = getattr(ctx, "quad", False)
+            if culled:
+                rec = torch.empty(n, 16, device=dev, dtype=torch.float32)
+                call("sfx_pack_raster_records", n, ptr(xys), ptr(conics), ptr(colors), ptr(opacity), ptr(rec), stream())
+                call("sfx_rasterize_fwd_views_quad", 1, tiles_x, tiles_y, 16, H, W, ptr(gids_sorted), ptr(tile_bins),
+                     ptr(rec), ptr(background), 0, ptr(final_Ts), ptr(final_idx), ptr(out), ptr(alpha), stream())
+            else:
+                call("sfx_rasterize_fwd", tiles_x, tiles_y, bw, H, W, ptr(gids_sorted), ptr(tile_bins), ptr(xys),
+                     ptr(conics), ptr(colors), ptr(opacity), ptr(background), ptr(final_Ts), ptr(final_idx), ptr(out),
+                     ptr(alpha), stream())
+        ctx.quad = culled and ctx.num_isect >= 1  # the backward over the culled list (an empty one included)
         ctx.img = (H, W, bw, tiles_x, tiles_y)
         ctx.save_for_backward(gids_sorted, tile_bins, xys, conics, colors, opacity, background, final_Ts, final_idx)
         if return_alpha:
@@ -273,24 +294,6 @@ def _all_culled(background, H, W, tiles_x, tiles_y):
             torch.zeros(tiles_x * tiles_y, 2, device=dev, dtype=torch.int32))
 
 
-def _culled_forward(n, xys, depths, radii, conics, colors, opacity, background, H, W, tiles_x, tiles_y, total, cum):
-    """The forward over the culled list (single view): _culled_list -> rasterize_fwd_views_quad.  Called when
-    gsplat's own list is non-empty."""
-    dev = xys.device
-    if total < 1:
-        return _all_culled(background, H, W, tiles_x, tiles_y)
-    gids_s, tile_bins = _culled_list(n, xys, depths, radii, conics, opacity, H, W, tiles_x, tiles_y, total, cum)
-    final_Ts = torch.empty(H, W, device=dev, dtype=torch.float32)
-    final_idx = torch.empty(H, W, device=dev, dtype=torch.int32)
-    rec = torch.empty(n, 16, device=dev, dtype=torch.float32)
-    call("sfx_pack_raster_records", n, ptr(xys), ptr(conics), ptr(colors), ptr(opacity), ptr(rec), stream())
-    out = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
-    alpha = torch.empty(H, W, device=dev, dtype=torch.float32)
-    call("sfx_rasterize_fwd_views_quad", 1, tiles_x, tiles_y, 16, H, W, ptr(gids_s), ptr(tile_bins), ptr(rec),
-         ptr(background), 0, ptr(final_Ts), ptr(final_idx), ptr(out), ptr(alpha), stream())
-    return out, alpha, final_Ts, final_idx, gids_s, tile_bins
-
-
 _ND_SLAB = 32  # channels per launch of the N-channel kernels (their largest tier)
 
 
@@ -309,30 +312,11 @@ class _RasterizeGaussiansND(torch.autograd.Function):
         H, W, bw = int(img_height), int(img_width), int(block_width)
         tiles_x, tiles_y = (W + bw - 1) // bw, (H + bw - 1) // bw
         xys, conics, colors, opacity, background = map(_f32, (xys, conics, colors, opacity, background))
-        radii = radii.to(torch.int32).contiguous()
-        culled = CULL and bw == 16 and n > 0
-        if culled:
-            num_isect, kept_total, kept_cum = _culled_counts(n, num_tiles_hit, xys, radii, conics, opacity, H, W,
-                                                             tiles_x, tiles_y)
+        ctx.num_isect, _, gids_sorted, tile_bins, early = _raster_lists(
+            xys, depths, radii, conics, num_tiles_hit, opacity, background, C, H, W, bw)
+        if early is not None:
+            out, alpha, final_Ts, final_idx = early
         else:
-            num_isect, cum = compute_cumulative_intersects(num_tiles_hit) if n else (0, None)
-        ctx.num_isect = num_isect
-        if num_isect < 1:
-            out = torch.ones(H, W, C, device=dev) * background
-            gids_sorted = torch.zeros(0, device=dev, dtype=torch.int32)
-            tile_bins = torch.zeros(0, 2, device=dev, dtype=torch.int32)
-            final_Ts = torch.zeros(H, W, device=dev)  # gsplat v0.1.11 empty-branch quirk (alpha == 1)
-            final_idx = torch.zeros(H, W, device=dev, dtype=torch.int32)
-            alpha = 1 - final_Ts
-        elif culled and kept_total < 1:
-            out, alpha, final_Ts, final_idx, gids_sorted, tile_bins = _all_culled(background, H, W, tiles_x, tiles_y)
-        else:
-            if culled:
-                gids_sorted, tile_bins = _culled_list(n, xys, _f32(depths), radii, conics, opacity, H, W, tiles_x,
-                                                      tiles_y, kept_total, kept_cum)
-            else:
-                _, _, _, gids_sorted, tile_bins = bin_and_sort_gaussians(n, num_isect, xys, _f32(depths), radii, cum,
-                                                                         (tiles_x, tiles_y, 1), bw)
             out = torch.empty(H, W, C, device=dev, dtype=torch.float32)
             final_Ts = torch.empty(H, W, device=dev, dtype=torch.float32)
             final_idx = torch.empty(H, W, device=dev, dtype=torch.int32)

@@ -1,4 +1,4 @@
-"""The render's exact contribution culling (csrc/render.hip cull_setup / cull_box_may_hit, ABI v9) restated in
+"""The render's exact contribution culling (csrc/raster_common.h cull_setup / cull_box_may_hit, ABI v9) restated in
 numpy float32 and checked for conservativeness on CPU: whenever the predicate drops a (Gaussian, pixel box) pair,
 the per-pixel test of the rasterizer (gsplat v0.1.11 rasterize_forward: sigma = 0.5 (a dx^2 + c dy^2) + b dx dy,
 alpha = min(0.999, o exp(-sigma)), skipped when sigma < 0 or alpha < 1/255) fails at every pixel centre of the box.
