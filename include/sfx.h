@@ -25,6 +25,12 @@ extern "C" {
 #define SFX_ERR_HIP -2
 #define SFX_ERR_WORKSPACE -3
 
+/* activation codes of a per-output-column epilogue (sfx_heads_cols, sfx_col_epilogue_fwd / _bwd) */
+#define SFX_COL_IDENTITY 0
+#define SFX_COL_TANH 1
+#define SFX_COL_SIGMOID 2
+#define SFX_COL_NEG_RELU 3 /* -max(z, 0): the direct-prediction scale clamp, feature_predictor.py:208-210 */
+
 /* ---- library ------------------------------------------------------------ */
 int sfx_abi_version(void);
 const char* sfx_last_error(void);
@@ -321,6 +327,19 @@ int sfx_segment_sum(int m, int C, const int* idx_ptr, const int* sorted_idx, con
  * every leading dimension >= N */
 int sfx_act_bwd(int M, int N, const float* dY, long long ldgy, const float* pre, long long ldp, int act, int ncols,
                 float* dX, long long lddx, void* stream);
+/* (ABI 16, additive) Per-column output epilogue of the FeaturePredictor heads in the training step and in the
+ * unfused eval chain, and its derivative.  col_act / col_res / col_add: DEVICE arrays of N entries (SFX_COL_* code,
+ * column of x that holds the residual base or < 0 for none, additive constant).
+ * sfx_col_epilogue_fwd: y[i][c] = act_c(z[i][c]) + col_add[c] + x[i][col_res[c]]; z is overwritten with what the
+ *   backward needs: the activated value for tanh and sigmoid, the pre-activation otherwise.  x may be NULL when no
+ *   column has a residual (the caller's promise); y must not alias z.
+ * sfx_col_epilogue_bwd: dz[i][c] = dy[i][c] * act_c'(saved[i][c]): 1 - s^2 (tanh), s (1 - s) (sigmoid), -1 where the
+ *   saved pre-activation is > 0 else 0 (neg-relu), 1 (identity); dz may alias dy.
+ * Every leading dimension >= N; M * N < 2^31. */
+int sfx_col_epilogue_fwd(int M, int N, float* z, long long ldz, const int* col_act, const int* col_res,
+                         const float* col_add, const float* x, long long ldx, float* y, long long ldy, void* stream);
+int sfx_col_epilogue_bwd(int M, int N, const float* dy, long long ldgy, const float* saved, long long lds,
+                         const int* col_act, float* dz, long long lddz, void* stream);
 /* (ABI v13) DropPath keep mask of n points (timm DropPath, pointtransformer_v3.py:145): out[i] = 1/keep or 0,
  * Bernoulli(keep) from a counter-based hash of (seed, i) -- deterministic for a given seed */
 int sfx_drop_mask(long long n, float keep, unsigned long long seed, float* out, void* stream);
@@ -495,6 +514,15 @@ int sfx_gs_pack(int n, const float* means, long long ld_means, const float* scal
                 const float* features_dc, long long ld_dc, const float* features_rest, long long ld_rest,
                 int rest_dim, float grid_resolution, float* feat, long long ld_feat, int* grid_coord, int* grid_max,
                 void* stream);
+/* (ABI 16, additive) The same batchify for any list of attributes: source s (nsrc <= 8; HOST arrays src / ld / width /
+ * dst_col of nsrc entries, src[s] a device pointer to rows of ld[s] floats) is copied to columns
+ * [dst_col[s], dst_col[s] + width[s]) of dst [n][ld_dst].  The caller lists the input features in `input_features`
+ * order and, behind them, the attributes that are only a residual base of a head (DESIGN.md "Head configurations").
+ * grid_coord = floor(means * res) and the grid max always come from `means`, listed or not (feature_predictor.py:
+ * 151-156); both may be NULL.  Destination ranges must lie inside a row and must not overlap. */
+int sfx_gs_pack_cols(int n, int nsrc, const float* const* src, const long long* ld, const int* width,
+                     const int* dst_col, const float* means, long long ld_means, float grid_resolution, float* dst,
+                     long long ld_dst, int* grid_coord, int* grid_max, void* stream);
 /* Pointcept offset2batch */
 int sfx_offsets_to_batch(int n, int B, const long long* offsets, int* batch, void* stream);
 /* (ABI v12) Row moves by index, rows of `words` 32-bit words (leading dimensions in words): scatter = 0 gathers
@@ -779,6 +807,16 @@ int sfx_heads_pack(int ng, int kin, int out_dim, const float* w1, int ld1, const
                    void* stream_);
 int sfx_heads(int M, int ng, int kin, int out_dim, const float* x, long long ldx, int res_off, int n_tanh,
               const int* ocols, const float* stream, const float* params, float* y, void* stream_);
+/* (ABI 16, additive) sfx_heads with a per-output-column epilogue, for every head wiring the reference accepts:
+ *   y[i][c] = act_c(z[i][c]) + col_add[c] + x[i][col_res[c]],  z = the heads' last-layer output,
+ * col_act[c] a SFX_COL_* code, col_res[c] the column of the input row (anywhere in [0, ldx), also past kin: the
+ * first layer reads only x[:, :kin]) that holds the residual base or < 0 for none, col_add[c] a constant (the fp32
+ * log(max_scale_normalized) of the scale clamp).  The three tables are HOST arrays of out_dim entries, as ocols is;
+ * they travel as kernel arguments and are staged in LDS next to b4.  sfx_heads is this entry with
+ * col_act = tanh on c < n_tanh, col_res[c] = res_off + c, col_add = 0, and gives the same bits. */
+int sfx_heads_cols(int M, int ng, int kin, int out_dim, const float* x, long long ldx, const int* ocols,
+                   const int* col_act, const int* col_res, const float* col_add, const float* stream,
+                   const float* params, float* y, void* stream_);
 
 /* (ABI 16, additive) LPIPS(net='vgg') building blocks (reference train.py:269-282, utils/metrics.py:13-17): the
  * frozen VGG16 feature stack on NHWC fp32 images [V][H][W][C] and the tap distance, forward and data backward (no

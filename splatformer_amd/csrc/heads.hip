@@ -1,6 +1,9 @@
 // FeaturePredictor output heads + residual in one launch (reference models/feature_predictor.py:74-94, :201-235):
 //   y = cat(backbone [N, 96], feat [N, Cin]);  per feature f: o_f = L4(ReLU(L3(ReLU(L2(ReLU(L1(y)))))))
 //   (Linear 119 -> 128 -> 128 -> 128 -> c_f), tanh on the means head, out_f = feat_f + o_f.
+// Every other head wiring the reference accepts (direct prediction with the scale clamp, any subset or order of
+// attributes, Identity / Tanh / Sigmoid per attribute, heads on the backbone feature alone) differs only in the
+// output epilogue, which a per-output-column table describes (sfx_heads_cols; DESIGN.md "Head configurations").
 //
 // The unfused form (one GEMM for the six first layers, two block-diagonal grouped GEMMs, one block-diagonal output
 // GEMM) writes and re-reads the [N, 768] hidden activation three times: ~1.5 GB per 100k-point refine.  Here every
@@ -31,6 +34,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int HW = 128;               // head width (feature_predictor.py:74: width 128)
 constexpr int MAXH = 6;               // heads
+constexpr int MAXO = 64;              // packed output columns
 constexpr int SLAB = 8192;            // [2 unit blocks][2 terms][32 rows][32 positions] fp16
 constexpr int PHASE = 2 * SLAB;
 constexpr int WAVES = 8;
@@ -44,9 +48,11 @@ struct HeadsArgs {
   int ng;              // heads
   int kin;             // input columns read (backbone width + Cin)
   int out_dim;         // packed output width = sum of head widths
-  int res_off;         // column of the residual record in the input row
-  int n_tanh;          // leading output columns with tanh (the means head)
   int ocol[MAXH + 1];  // output column of head g (ocol[ng] = out_dim)
+  // epilogue of output column c: y = act(z) + add + x[res] (sfx.h SFX_COL_*; res < 0: no residual)
+  signed char act[MAXO];
+  int res[MAXO];
+  float add[MAXO];
 };
 
 __device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
@@ -59,7 +65,8 @@ __device__ __forceinline__ void wait_vm_lgkm() {
 }
 
 // params (floats): [(g*3 + L) * 256 + 2 * ((ob * 2 + h) * 16 + i)] = (1/s_u, b_u) of unit u = 32 ob + acc_row(i, h)
-// of layer L of head g; then W4 rows (out_dim x 128, natural order) at W4_OFF; then b4 (out_dim) at B4_OFF.
+// of layer L of head g; then W4 rows (out_dim x 128, natural order) at W4_OFF; then b4 (out_dim) at B4_OFF.  In LDS
+// the kernel stages the launch's column table behind them, at npar: 3 words (act, res, add) per output column.
 constexpr int W4_OFF = MAXH * 3 * 256;
 __host__ __device__ constexpr int b4_off(int out_dim) { return W4_OFF + out_dim * HW; }
 
@@ -95,6 +102,11 @@ heads_kernel(int M, const float* __restrict__ X, long long ldx, const float* __r
     if (P0 + q < NP) issue(P0 + q);
 
   for (int i = tid; i < npar; i += WAVES * 64) s_par[i] = par[i];
+  if (tid < a.out_dim) {
+    s_par[npar + 3 * tid] = __int_as_float((int)a.act[tid]);
+    s_par[npar + 3 * tid + 1] = __int_as_float(a.res[tid]);
+    s_par[npar + 3 * tid + 2] = a.add[tid];
+  }
 
   // ---- the point's input row: channels 16 t + 8 h + 0..7 of k-step t, zero past kin ----
   const __amdgpu_buffer_rsrc_t rX = rsrc_ext(X, (unsigned)M * (unsigned)ldx * 4u);
@@ -237,9 +249,15 @@ heads_kernel(int M, const float* __restrict__ X, long long ldx, const float* __r
             for (int i = 0; i < 16; ++i) s = fmaf(wr[32 * ob + acc_row(i, h)], acc[ob][i], s);
           s += __shfl_xor(s, 32, 64);
           if (h == 0 && pok) {
+            const float* tb = s_par + npar + 3 * c;  // (wave-uniform: LDS broadcasts)
+            const int code = __float_as_int(tb[0]), rc = __float_as_int(tb[1]);
             float z = s + b4[c];
-            if (c < a.n_tanh) z = tanhf(z);
-            Y[(long long)prow * a.out_dim + c] = X[(long long)prow * ldx + a.res_off + c] + z;
+            if (code == SFX_COL_TANH) z = tanhf(z);
+            else if (code == SFX_COL_SIGMOID) z = 1.f / (1.f + expf(-z));
+            else if (code == SFX_COL_NEG_RELU) z = -fmaxf(z, 0.f);
+            if (tb[2] != 0.f) z += tb[2];
+            if (rc >= 0) z = X[(long long)prow * ldx + rc] + z;
+            Y[(long long)prow * a.out_dim + c] = z;
           }
         }
       }
@@ -348,24 +366,33 @@ int sfx_heads_pack(int ng, int kin, int out_dim, const float* w1, int ld1, const
   return sfx::check_launch("sfx_heads_pack");
 }
 
-// Y [M, out_dim] = heads(X[:, :kin]) + X[:, res_off : res_off + out_dim], tanh on the first n_tanh columns
-int sfx_heads(int M, int ng, int kin, int out_dim, const float* x, long long ldx, int res_off, int n_tanh,
-              const int* ocols, const float* stream, const float* params, float* y, void* stream_) {
-  SFX_REQUIRE(M >= 0 && heads_ok(ng, kin, out_dim), "sfx_heads: unsupported head shape");
+// Y [M, out_dim]: column c = act_c(heads(X[:, :kin])[c]) + col_add[c] + X[:, col_res[c]] (col_res[c] < 0: none);
+// the three tables are host arrays of out_dim entries
+int sfx_heads_cols(int M, int ng, int kin, int out_dim, const float* x, long long ldx, const int* ocols,
+                   const int* col_act, const int* col_res, const float* col_add, const float* stream,
+                   const float* params, float* y, void* stream_) {
+  SFX_REQUIRE(M >= 0 && heads_ok(ng, kin, out_dim), "sfx_heads_cols: unsupported head shape");
   if (M == 0) return SFX_OK;
-  SFX_REQUIRE(x && ocols && stream && params && y && ldx >= kin && res_off + out_dim <= ldx,
-              "sfx_heads: bad arguments");
+  SFX_REQUIRE(x && ocols && col_act && col_res && col_add && stream && params && y && ldx >= kin,
+              "sfx_heads_cols: bad arguments");
   SFX_REQUIRE((reinterpret_cast<uintptr_t>(stream) & 15) == 0 && ldx % 4 == 0 &&
                   (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (long long)M * ldx * 4 + 64 < (long long)OOB,
-              "sfx_heads: alignment / size");
+              "sfx_heads_cols: alignment / size");
   HeadsArgs a;
   a.ng = ng;
   a.kin = kin;
   a.out_dim = out_dim;
-  a.res_off = res_off;
-  a.n_tanh = n_tanh;
   for (int g = 0; g <= MAXH; ++g) a.ocol[g] = g <= ng ? ocols[g] : out_dim;
-  SFX_REQUIRE(a.ocol[0] == 0 && a.ocol[ng] == out_dim, "sfx_heads: column table");
+  SFX_REQUIRE(a.ocol[0] == 0 && a.ocol[ng] == out_dim, "sfx_heads_cols: column table");
+  for (int g = 0; g < ng; ++g) SFX_REQUIRE(a.ocol[g] < a.ocol[g + 1], "sfx_heads_cols: column table");
+  for (int c = 0; c < MAXO; ++c) {
+    const bool on = c < out_dim;
+    SFX_REQUIRE(!on || (col_act[c] >= SFX_COL_IDENTITY && col_act[c] <= SFX_COL_NEG_RELU && col_res[c] < ldx),
+                "sfx_heads_cols: epilogue table (activation code or residual column out of range)");
+    a.act[c] = (signed char)(on ? col_act[c] : 0);
+    a.res[c] = on && col_res[c] >= 0 ? col_res[c] : -1;
+    a.add[c] = on ? col_add[c] : 0.f;
+  }
   const int npar = (int)sfx_heads_params_floats(out_dim);
   hipStream_t st = sfx::as_stream(stream_);
   const unsigned blocks = sfx::ceil_div(M, WAVES * 32);
@@ -389,12 +416,30 @@ int sfx_heads(int M, int ng, int kin, int out_dim, const float* x, long long ldx
   }
   const int gper = ng / S;
   const dim3 grid(blocks, (unsigned)S);
-  const size_t dyn = (size_t)npar * 4;
+  const size_t dyn = (size_t)(npar + 3 * out_dim) * 4;  // parameters + the staged column table
   if (kin <= 128)
     heads_kernel<128><<<grid, WAVES * 64, dyn, st>>>(M, x, ldx, stream, params, npar, a, y, gper);
   else
     heads_kernel<160><<<grid, WAVES * 64, dyn, st>>>(M, x, ldx, stream, params, npar, a, y, gper);
-  return sfx::check_launch("sfx_heads");
+  return sfx::check_launch("sfx_heads_cols");
+}
+
+// Y [M, out_dim] = heads(X[:, :kin]) + X[:, res_off : res_off + out_dim], tanh on the first n_tanh columns: the
+// table of the ptv3_base.gin wiring
+int sfx_heads(int M, int ng, int kin, int out_dim, const float* x, long long ldx, int res_off, int n_tanh,
+              const int* ocols, const float* stream, const float* params, float* y, void* stream_) {
+  SFX_REQUIRE(M >= 0 && heads_ok(ng, kin, out_dim), "sfx_heads: unsupported head shape");
+  if (M == 0) return SFX_OK;
+  SFX_REQUIRE(x && ocols && stream && params && y && ldx >= kin && res_off >= 0 && res_off + out_dim <= ldx,
+              "sfx_heads: bad arguments");
+  int act[MAXO], res[MAXO];
+  float add[MAXO];
+  for (int c = 0; c < out_dim; ++c) {
+    act[c] = c < n_tanh ? SFX_COL_TANH : SFX_COL_IDENTITY;
+    res[c] = res_off + c;
+    add[c] = 0.f;
+  }
+  return sfx_heads_cols(M, ng, kin, out_dim, x, ldx, ocols, act, res, add, stream, params, y, stream_);
 }
 
 }  // extern "C"

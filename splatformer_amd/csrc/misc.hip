@@ -53,6 +53,50 @@ __global__ void __launch_bounds__(256) gs_pack_kernel(int n, const float* __rest
   }
 }
 
+// gs_pack_kernel for any list of attributes (sfx_gs_pack_cols): the packed element space is [n][W + 3], W = the
+// sources' total width in list order; virtual columns W..W+2 are `means` again, read only for grid_coord and the
+// grid max (means need not be a listed source).  Source s goes to columns dcol[s].. of the destination row.
+constexpr int PACK_MAXSRC = 8;
+struct PackCols {
+  const float* src[PACK_MAXSRC];
+  long long ld[PACK_MAXSRC];
+  int end[PACK_MAXSRC];   // end of source s in the packed element space (cumulative widths)
+  int dcol[PACK_MAXSRC];
+  int nsrc;
+};
+
+__global__ void __launch_bounds__(256) gs_pack_cols_kernel(int n, PackCols p, int W, const float* __restrict__ means,
+                                                           long long ld_m, float grid_resolution,
+                                                           float* __restrict__ dst, long long ld_d,
+                                                           int* __restrict__ grid_coord, int* __restrict__ grid_max) {
+  const unsigned WT = (unsigned)W + (grid_coord ? 3u : 0u);
+  const unsigned total = (unsigned)n * WT;
+  int mx = 0;
+  for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < total; e += gridDim.x * 256u) {
+    const unsigned i = e / WT;
+    const int c = (int)(e - i * WT);
+    if (c < W) {
+      int s = 0, start = 0;
+      while (c >= p.end[s]) start = p.end[s++];  // (c < W = end[nsrc - 1]: s stays below nsrc)
+      dst[i * ld_d + p.dcol[s] + (c - start)] = p.src[s][i * p.ld[s] + (c - start)];
+    } else {
+      const int g = (int)floorf(means[i * ld_m + (c - W)] * grid_resolution);
+      grid_coord[3ll * i + (c - W)] = g;
+      mx = max(mx, g);
+    }
+  }
+  if (grid_coord && grid_max) {  // all lanes reach this: wave-reduce, then one atomic per workgroup
+    __shared__ int wmx[4];
+    mx = sfx::wave_max_i(mx);
+    if ((threadIdx.x & 63) == 0) wmx[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      mx = max(max(wmx[0], wmx[1]), max(wmx[2], wmx[3]));
+      if (mx > 0) atomicMax(grid_max, mx);
+    }
+  }
+}
+
 // y[i, o] = GELU((sum_k x[i, k] W[o, k] + b[o]) * scale[o] + shift[o]) for K <= 64 input features: fp32 FMA
 // chains on the VALU (the MFMA GEMM's tiles are built for K >= 64; at K = 23 its launch ran at 7.6 TF/s).
 // 256 threads = 64 points x 4 threads, each thread N/4 outputs of its point; W^T, bias, scale, shift in LDS.
@@ -153,6 +197,41 @@ int sfx_gs_pack(int n, const float* means, long long ld_means, const float* scal
       n, means, ld_means, scales, ld_scales, opacities, ld_opacities, quats, ld_quats, features_dc, ld_dc,
       features_rest, ld_rest, rest_dim, grid_resolution, feat, ld_feat, grid_coord, grid_max);
   return sfx::check_launch("sfx_gs_pack");
+}
+
+int sfx_gs_pack_cols(int n, int nsrc, const float* const* src, const long long* ld, const int* width,
+                     const int* dst_col, const float* means, long long ld_means, float grid_resolution, float* dst,
+                     long long ld_dst, int* grid_coord, int* grid_max, void* stream) {
+  SFX_REQUIRE(n >= 0 && nsrc >= 1 && nsrc <= PACK_MAXSRC, "sfx_gs_pack_cols: bad sizes (1..8 sources)");
+  if (n == 0) return SFX_OK;
+  SFX_REQUIRE(src && ld && width && dst_col && dst && (!grid_coord || means), "sfx_gs_pack_cols: null buffer");
+  SFX_REQUIRE(!grid_coord || ld_means >= 3, "sfx_gs_pack_cols: ld_means < 3");
+  PackCols p;
+  int W = 0;
+  for (int s = 0; s < PACK_MAXSRC; ++s) {
+    const bool on = s < nsrc;
+    if (on) {
+      SFX_REQUIRE(src[s] && width[s] >= 1 && ld[s] >= width[s], "sfx_gs_pack_cols: bad source (null, width < 1 or "
+                                                                 "row stride below the width)");
+      SFX_REQUIRE(dst_col[s] >= 0 && (long long)dst_col[s] + width[s] <= ld_dst,
+                  "sfx_gs_pack_cols: destination columns outside the row");
+      for (int t = 0; t < s; ++t)
+        SFX_REQUIRE(dst_col[s] >= dst_col[t] + width[t] || dst_col[t] >= dst_col[s] + width[s],
+                    "sfx_gs_pack_cols: destination column ranges overlap");
+      W += width[s];
+    }
+    p.src[s] = on ? src[s] : nullptr;
+    p.ld[s] = on ? ld[s] : 0;
+    p.end[s] = W;
+    p.dcol[s] = on ? dst_col[s] : 0;
+  }
+  p.nsrc = nsrc;
+  const long long total = (long long)n * (W + 3);
+  SFX_REQUIRE(total < (1ll << 31), "sfx_gs_pack_cols: n * record width must fit int32");
+  const unsigned blocks = sfx::ceil_div(total, 256);
+  gs_pack_cols_kernel<<<blocks < 512u ? blocks : 512u, 256, 0, sfx::as_stream(stream)>>>(
+      n, p, W, means, ld_means, grid_resolution, dst, ld_dst, grid_coord, grid_max);
+  return sfx::check_launch("sfx_gs_pack_cols");
 }
 
 // Embedding (reference pointtransformer_v3.py:273-278: Linear(Cin, C) -> BatchNorm1d (eval, as scale/shift) ->

@@ -463,6 +463,49 @@ __global__ void __launch_bounds__(256) act_bwd_kernel(int M, int N, const float*
   dX[(long long)m * lddx + c] = g;
 }
 
+// ---- per-column head epilogue (sfx.h SFX_COL_*) and its derivative -------------------------------------
+// y = act_c(z) + add_c + x[res_c]; z <- what the derivative reads (the activated value of tanh / sigmoid, else z)
+__global__ void __launch_bounds__(256) col_epilogue_fwd_kernel(int M, int N, float* __restrict__ Z, long long ldz,
+                                                               const int* __restrict__ col_act,
+                                                               const int* __restrict__ col_res,
+                                                               const float* __restrict__ col_add,
+                                                               const float* __restrict__ X, long long ldx,
+                                                               float* __restrict__ Y, long long ldy) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)M * N) return;
+  const int m = (int)(e / N), c = (int)(e - (long long)m * N);
+  const int code = col_act[c], rc = col_res[c];
+  const float z = Z[(long long)m * ldz + c];
+  // tanh / sigmoid in fp64, rounded once: the derivative is taken from the stored value, and 1 - s amplifies an
+  // error of s as the activation saturates (the kernel is bound by its four memory streams, not by this)
+  float v = z;
+  if (code == SFX_COL_TANH) v = (float)tanh((double)z);
+  else if (code == SFX_COL_SIGMOID) v = (float)(1.0 / (1.0 + exp(-(double)z)));
+  else if (code == SFX_COL_NEG_RELU) v = -fmaxf(z, 0.f);
+  if (code == SFX_COL_TANH || code == SFX_COL_SIGMOID) Z[(long long)m * ldz + c] = v;
+  double y = (double)v + (double)col_add[c];
+  if (rc >= 0) y += (double)X[(long long)m * ldx + rc];
+  Y[(long long)m * ldy + c] = (float)y;
+}
+
+__global__ void __launch_bounds__(256) col_epilogue_bwd_kernel(int M, int N, const float* dY, long long ldgy,
+                                                               const float* __restrict__ S, long long lds,
+                                                               const int* __restrict__ col_act, float* dZ,
+                                                               long long lddz) {  // (dZ may be dY)
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)M * N) return;
+  const int m = (int)(e / N), c = (int)(e - (long long)m * N);
+  const int code = col_act[c];
+  float g = dY[(long long)m * ldgy + c];
+  if (code != SFX_COL_IDENTITY) {
+    const float sf = S[(long long)m * lds + c];
+    const double s = (double)sf;  // (the products in fp64, one rounding)
+    g = (float)((double)g * (code == SFX_COL_TANH ? 1.0 - s * s
+                             : code == SFX_COL_SIGMOID ? s * (1.0 - s) : (sf > 0.f ? -1.0 : 0.0)));
+  }
+  dZ[(long long)m * lddz + c] = g;
+}
+
 // ---- DropPath keep masks ------------------------------------------------------------------------------
 // timm DropPath per point (reference pointtransformer_v3.py:145, drop_path=0.3 schedule): out[i] = 1/keep when
 // u_i < keep, else 0, with u_i uniform on [0, 1) in 2^-24 steps from a counter-based hash of (seed, i) (splitmix64
@@ -696,6 +739,28 @@ int sfx_act_bwd(int M, int N, const float* dY, long long ldgy, const float* pre,
   act_bwd_kernel<<<sfx::ceil_div((long long)M * N, 256), 256, 0, sfx::as_stream(stream)>>>(M, N, dY, ldgy, pre, ldp,
                                                                                            act, ncols, dX, lddx);
   return sfx::check_launch("sfx_act_bwd");
+}
+
+int sfx_col_epilogue_fwd(int M, int N, float* z, long long ldz, const int* col_act, const int* col_res,
+                         const float* col_add, const float* x, long long ldx, float* y, long long ldy, void* stream) {
+  SFX_REQUIRE(M >= 0 && N > 0 && (long long)M * N < (1ll << 31), "sfx_col_epilogue_fwd: bad sizes");
+  if (M == 0) return SFX_OK;
+  SFX_REQUIRE(z && col_act && col_res && col_add && y && y != z, "sfx_col_epilogue_fwd: null buffer (or y == z)");
+  SFX_REQUIRE(ldz >= N && ldy >= N, "sfx_col_epilogue_fwd: leading dim");
+  col_epilogue_fwd_kernel<<<sfx::ceil_div((long long)M * N, 256), 256, 0, sfx::as_stream(stream)>>>(
+      M, N, z, ldz, col_act, col_res, col_add, x, ldx, y, ldy);
+  return sfx::check_launch("sfx_col_epilogue_fwd");
+}
+
+int sfx_col_epilogue_bwd(int M, int N, const float* dy, long long ldgy, const float* saved, long long lds,
+                         const int* col_act, float* dz, long long lddz, void* stream) {
+  SFX_REQUIRE(M >= 0 && N > 0 && (long long)M * N < (1ll << 31), "sfx_col_epilogue_bwd: bad sizes");
+  if (M == 0) return SFX_OK;
+  SFX_REQUIRE(dy && saved && col_act && dz, "sfx_col_epilogue_bwd: null buffer");
+  SFX_REQUIRE(ldgy >= N && lds >= N && lddz >= N, "sfx_col_epilogue_bwd: leading dim");
+  col_epilogue_bwd_kernel<<<sfx::ceil_div((long long)M * N, 256), 256, 0, sfx::as_stream(stream)>>>(
+      M, N, dy, ldgy, saved, lds, col_act, dz, lddz);
+  return sfx::check_launch("sfx_col_epilogue_bwd");
 }
 
 int sfx_sumsq(long long n, const float* x, double* out, void* stream) {

@@ -45,6 +45,23 @@ def _channels(sh_degree):
     return d
 
 
+_ACTIVATIONS = {"identity": nn.Identity, "tanh": nn.Tanh, "sigmoid": nn.Sigmoid}  # what the reference registers
+
+
+def _activation_name(feature: str, a) -> str:
+    """'identity' | 'tanh' | 'sigmoid' of a res_feature_activation entry: a module instance, a module class or a
+    name (any case, as gin writes it: 'Tanh', '@torch.nn.Tanh()')."""
+    if isinstance(a, str):
+        nm = a.strip().lstrip("@").rstrip("()").split(".")[-1].lower()
+        if nm in _ACTIVATIONS:
+            return nm
+    else:
+        for nm, cls in _ACTIVATIONS.items():
+            if a is cls or type(a) is cls:
+                return nm
+    raise ValueError(f"res_feature_activation[{feature!r}] = {a!r}: expected Identity, Tanh or Sigmoid")
+
+
 class FeaturePredictor(nn.Module):
     def __init__(self, backbone_type="PT", sh_degree=1, input_features=BASE_FEATURES, input_feat_to_mlp=True,
                  output_features=BASE_FEATURES, output_head_nlayer=4, output_head_type="mlp-relu",
@@ -54,34 +71,49 @@ class FeaturePredictor(nn.Module):
         super().__init__()
         if backbone_type != "PT":
             raise NotImplementedError("backbone_type 'SP' (SparseUNet) is out of scope (SURVEY.md §2)")
-        if output_head_type != "mlp-relu" or output_features_type != "res" or not input_feat_to_mlp:
-            raise NotImplementedError("only the ptv3_base.gin head configuration is on the path")
+        if output_head_type != "mlp-relu":
+            raise NotImplementedError("output_head_type: only 'mlp-relu' exists (the reference raises too)")
+        if output_features_type not in ("res", "dc"):
+            raise ValueError(f"output_features_type {output_features_type!r}: expected 'res' or 'dc'")
         ch = _channels(sh_degree)
         self.sh_degree = sh_degree
+        for arg, feats in (("input_features", input_features), ("output_features", output_features)):
+            for f in feats:
+                if f not in FEATURE2CHANNEL:
+                    raise ValueError(f"{arg}: unknown attribute {f!r} (known: {ALL_FEATURES})")
+            if len(set(feats)) != len(feats):
+                raise ValueError(f"{arg}: an attribute is listed twice in {list(feats)}")
         self.input_features = [f for f in input_features if not (f == "features_rest" and sh_degree == 0)]
         self.output_features = [f for f in output_features if not (f == "features_rest" and sh_degree == 0)]
-        if self.input_features != [f for f in BASE_FEATURES if f in self.input_features]:
-            raise NotImplementedError("input_features must follow ptv3_base.gin order")
-        if self.output_features != self.input_features:
-            raise NotImplementedError("output_features must equal input_features (ptv3_base.gin)")
+        if not self.output_features:
+            raise ValueError("output_features: empty (no head to build)")
+        if not self.input_features:
+            raise ValueError("input_features: empty (the backbone needs an input feature)")
         self.ch = ch
         in_channels = sum(ch[f] for f in self.input_features)
         self.gs_features_dim = in_channels
         self.grid_resolution = grid_resolution
         self.max_scale_normalized = max_scale_normalized
         self.output_features_type = output_features_type
+        self.input_feat_to_mlp = bool(input_feat_to_mlp)
         self.additional_info = additional_info or {}
         self.res_activation = {f: "tanh" if f == "means" else "identity" for f in self.output_features}
-        if res_feature_activation is not None:
-            for f, a in res_feature_activation.items():
-                nm = type(a).__name__.lower() if not isinstance(a, str) else a.lower()
-                self.res_activation[f] = "tanh" if "tanh" in nm else "identity"
-            if any(self.res_activation[f] != ("tanh" if f == "means" else "identity") for f in self.output_features):
-                raise NotImplementedError("res_feature_activation must be Tanh(means), Identity(others)")
+        for f, a in (res_feature_activation or {}).items():
+            if f not in FEATURE2CHANNEL:
+                raise ValueError(f"res_feature_activation: unknown attribute {f!r}")
+            name = _activation_name(f, a)
+            if f in self.res_activation:
+                self.res_activation[f] = name
         self.backbone = PointTransformerV3Model(in_channels=in_channels, additional_info=additional_info,
                                                 **(backbone_kwargs or {}))
-        head_in = self.backbone.output_dim + in_channels
+        head_in = self.backbone.output_dim + (in_channels if self.input_feat_to_mlp else 0)
         self.head_in = head_in
+        # ptv3_base.gin's wiring keeps its own two entry points (sfx_gs_pack, sfx_heads) and the training step's
+        # leading-columns epilogue; every other wiring goes through the column-table entries
+        self.base_wiring = (
+            self.input_features == [f for f in BASE_FEATURES if not (f == "features_rest" and sh_degree == 0)] and self.output_features == self.input_features and output_features_type == "res"
+            and self.input_feat_to_mlp
+            and all(a == ("tanh" if f == "means" else "identity") for f, a in self.res_activation.items()))
         self.nlayer = output_head_nlayer
         self.width = output_head_width
         self.features_outputhead = nn.ModuleDict()
@@ -135,27 +167,90 @@ class FeaturePredictor(nn.Module):
         self._pack_cache = (key, packed)
         return packed
 
-    @torch.no_grad()
-    def refine_packed(self, gs: Dict[str, Tensor], perms=None) -> Tensor:
-        """One scene -> packed refined record [N, Cin] (input_features layout)."""
+    # ---- head input row and output epilogue ------------------------------------------------------------------
+    def row_layout(self):
+        """(ld, feature columns, residual-only columns) of the head input row H0 = [backbone | feat | pad to 4 |
+        residual-only attributes | pad to 4]: name -> first column.  `feat` holds the input features in their order
+        (the backbone reads it there; the heads too when input_feat_to_mlp).  A 'res' output that is no input has
+        its residual base behind the padded feat, in columns no first layer reads."""
+        cb = self.backbone.output_dim
+        fcol, c = OrderedDict(), cb
+        for f in self.input_features:
+            fcol[f] = c
+            c += self.ch[f]
+        c = (c + 3) // 4 * 4
+        rcol = OrderedDict()
+        if self.output_features_type == "res":
+            for f in self.output_features:
+                if f not in fcol:
+                    rcol[f] = c
+                    c += self.ch[f]
+        return (c + 3) // 4 * 4, fcol, rcol
+
+    def epilogue_table(self):
+        """(act, res, add): per packed output column the activation code (ptv3_ops.COL_*), the column of the head
+        input row that holds its residual base (-1: none) and an additive constant -- what sfx_heads_cols and the
+        col_epilogue kernels apply to the heads' last-layer output (reference feature_predictor.py:205-233)."""
+        _, fcol, rcol = self.row_layout()
+        code = {"identity": ops.COL_IDENTITY, "tanh": ops.COL_TANH, "sigmoid": ops.COL_SIGMOID}
+        act, res, add = [], [], []
+        for f in self.output_features:
+            for j in range(self.ch[f]):
+                if self.output_features_type == "res":
+                    act.append(code[self.res_activation[f]])
+                    res.append((fcol[f] if f in fcol else rcol[f]) + j)
+                    add.append(0.0)
+                elif f == "scales" and self.max_scale_normalized > 0:  # -relu(z) + log(max), the log in fp32
+                    act.append(ops.COL_NEG_RELU)
+                    res.append(-1)
+                    add.append(float(torch.log(torch.tensor(self.max_scale_normalized, dtype=torch.float32))))
+                else:
+                    act.append(ops.COL_IDENTITY)
+                    res.append(-1)
+                    add.append(0.0)
+        return act, res, add
+
+    def col_table(self, device) -> "ops.ColTable":
+        """epilogue_table() on `device` (built once per device)."""
+        tab = self.__dict__.get("_col_table")
+        if tab is None or tab.device != torch.device(device):
+            tab = ops.ColTable(self.epilogue_table(), device)
+            self.__dict__["_col_table"] = tab
+        return tab
+
+    def pack_input(self, gs: Dict[str, Tensor]):
+        """Batchify one scene: (h0 [N, ld] zeroed with feat and the residual-only attributes in place, the feat
+        view, grid_coord [N, 3] int32, grid max [1] int32)."""
         means = gs["means"]
-        _lib.require_gpu(means)
         dev = means.device
         n = means.shape[0]
-        cin = self.gs_features_dim
+        cb, cin = self.backbone.output_dim, self.gs_features_dim
+        ld, fcol, rcol = self.row_layout()
+        h0 = torch.zeros(n, ld, device=dev, dtype=torch.float32)
+        feat = h0[:, cb:cb + cin]
+        grid = torch.empty(n, 3, device=dev, dtype=torch.int32)
+        gmax = torch.zeros(1, device=dev, dtype=torch.int32)
+        if self.base_wiring:
+            ops.gs_pack(gs, feat, float(self.grid_resolution), grid, gmax)
+        else:
+            srcs = [(gs[f], c) for f, c in list(fcol.items()) + list(rcol.items())]
+            ops.gs_pack_cols(srcs, means, h0, float(self.grid_resolution), grid, gmax)
+        return h0, feat, grid, gmax
+
+    @torch.no_grad()
+    def refine_packed(self, gs: Dict[str, Tensor], perms=None) -> Tensor:
+        """One scene -> packed refined record [N, sum of output widths] (output_features order, columns())."""
+        means = gs["means"]
+        _lib.require_gpu(means)
+        n = means.shape[0]
         cb = self.backbone.output_dim
-        ld = (cb + cin + 3) // 4 * 4
         n_tanh = self.ch["means"] if self.output_features[0] == "means" else 0
         fused_heads = ops.heads_fused_ok(len(self.output_features), self.nlayer, self.width, self.head_in,
                                          sum(self.ch[f] for f in self.output_features))
         # the heads' pack check (a version key over every head parameter) runs here, while the GPU still
         # renders the previous scene, not between the backbone's last launch and the heads' (a host gap)
         heads_pack = self._fused_heads() if fused_heads else None
-        h0 = torch.zeros(n, ld, device=dev, dtype=torch.float32)
-        feat = h0[:, cb:cb + cin]
-        grid = torch.empty(n, 3, device=dev, dtype=torch.int32)
-        gmax = torch.zeros(1, device=dev, dtype=torch.int32)
-        ops.gs_pack(gs, feat, float(self.grid_resolution), grid, gmax)
+        h0, feat, grid, gmax = self.pack_input(gs)
         # Pointcept: int(grid_coord.max()).bit_length(), read back asynchronously (the backbone's embedding
         # GEMM runs while the host waits for it)
         data = {"coord": means, "grid_coord": grid, "offset": [n], "feat": feat,
@@ -173,13 +268,23 @@ class FeaturePredictor(nn.Module):
         if heads_pack is not None:
             st, pr, ocols, out_dim = heads_pack
             # all six heads + tanh + residual in one launch (csrc/heads.hip): no [N, 768] hidden in HBM
-            return ops.heads(h0, self.head_in, cb, out_dim, n_tanh, ocols, st, pr)
+            if self.base_wiring:
+                return ops.heads(h0, self.head_in, cb, out_dim, n_tanh, ocols, st, pr)
+            return ops.heads_cols(h0, self.head_in, out_dim, ocols, self._host_table(), st, pr)
         w1, b1, mids, wl, bl, out_dim = self._packed_heads()
         x = h0[:, :w1.shape[1]]  # [y | feat | 0-pad]
         h = ops.linear(x, w1, b1, act=ops.ACT_RELU)
         for wm, bm in mids:
             h = ops.grouped_linear(h, wm, bm, len(self.output_features), act=ops.ACT_RELU)
-        return ops.linear(h, wl, bl, act=ops.ACT_TANH, act_ncols=n_tanh, residual=feat)
+        if self.base_wiring:
+            return ops.linear(h, wl, bl, act=ops.ACT_TANH, act_ncols=n_tanh, residual=feat)
+        return ops.col_epilogue(ops.linear(h, wl, bl), self.col_table(h0.device), h0)
+
+    def _host_table(self):
+        tab = self.__dict__.get("_host_table_cache")
+        if tab is None:
+            tab = self.__dict__["_host_table_cache"] = self.epilogue_table()
+        return tab
 
     def check_refine(self, wait: bool = True) -> None:
         """Validate the pooled run counts of the refines issued so far (PointTransformerV3.check_deferred): call

@@ -262,6 +262,91 @@ def heads(x: Tensor, kin: int, res_off: int, out_dim: int, n_tanh: int, ocols: L
     return y
 
 
+# per-output-column epilogue codes (include/sfx.h SFX_COL_*)
+COL_IDENTITY, COL_TANH, COL_SIGMOID, COL_NEG_RELU = 0, 1, 2, 3
+
+
+def heads_base_table(res_off: int, n_tanh: int, out_dim: int) -> Tuple[List[int], List[int], List[float]]:
+    """The column table (act, res, add) that says what sfx_heads' (res_off, n_tanh) says."""
+    return ([COL_TANH if c < n_tanh else COL_IDENTITY for c in range(out_dim)],
+            [res_off + c for c in range(out_dim)], [0.0] * out_dim)
+
+
+def heads_cols(x: Tensor, kin: int, out_dim: int, ocols: List[int], table, st: Tensor, pr: Tensor) -> Tensor:
+    """y [N, out_dim]: column c = act_c(heads(x[:, :kin])[c]) + add[c] + x[:, res[c]] with table = (act, res, add),
+    three host lists of out_dim entries (res[c] < 0: no residual) -- sfx_heads_cols."""
+    act, res, add = table
+    if not (len(act) == len(res) == len(add) == out_dim):
+        raise RuntimeError("heads_cols: the column table must have out_dim entries")
+    M = x.shape[0]
+    px, ldx = _rows(x)
+    y = torch.empty(M, out_dim, device=x.device, dtype=torch.float32)
+    oc = (ctypes.c_int * len(ocols))(*ocols)
+    ca = (ctypes.c_int * out_dim)(*act)
+    cr = (ctypes.c_int * out_dim)(*res)
+    cd = (ctypes.c_float * out_dim)(*add)
+    call("sfx_heads_cols", M, len(ocols) - 1, kin, out_dim, px, ldx, oc, ca, cr, cd, ptr(st), ptr(pr), ptr(y),
+         stream())
+    return y
+
+
+class ColTable:
+    """A column table on the device, for the epilogue kernels of the training step and the unfused chain."""
+
+    def __init__(self, table, device):
+        self.act, self.res, self.add = [list(t) for t in table]
+        self.n = len(self.act)
+        self.d_act = torch.tensor(self.act, dtype=torch.int32, device=device)
+        self.d_res = torch.tensor(self.res, dtype=torch.int32, device=device)
+        self.d_add = torch.tensor(self.add, dtype=torch.float32, device=device)
+        self.device = torch.device(device)
+
+
+def col_epilogue(z: Tensor, tab: ColTable, x: Optional[Tensor]) -> Tensor:
+    """y = act_c(z) + add_c + x[:, res_c] per column (sfx_col_epilogue_fwd).  `z` is overwritten with what
+    train_ops.col_epilogue_bwd reads: the activated value of a tanh / sigmoid column, the pre-activation else."""
+    M, N = z.shape
+    if N != tab.n:
+        raise RuntimeError(f"col_epilogue: z has {N} columns, the table {tab.n}")
+    pz, ldz = _rows(z)
+    need_x = any(r >= 0 for r in tab.res)
+    if need_x and (x is None or max(tab.res) >= x.shape[1] or x.shape[0] != M):
+        raise RuntimeError("col_epilogue: a residual column lies outside x")
+    px, ldx = _rows(x) if need_x else (None, 0)
+    y = torch.empty(M, N, device=z.device, dtype=torch.float32)
+    call("sfx_col_epilogue_fwd", M, N, pz, ldz, ptr(tab.d_act), ptr(tab.d_res), ptr(tab.d_add), px, ldx, ptr(y), N,
+         stream())
+    return y
+
+
+def gs_pack_cols(sources: List[Tuple[Tensor, int]], means: Tensor, dst: Tensor, grid_resolution: float,
+                 grid_out: Optional[Tensor], grid_max: Optional[Tensor] = None) -> None:
+    """Batchify for any attribute list (sfx_gs_pack_cols): each (tensor [N, ...], first destination column) is
+    copied, flattened, into `dst` [N, ld]; grid_coord = floor(means * grid_resolution) and its maximum come from
+    `means` whether it is listed or not."""
+    n = means.shape[0]
+    keep, ps, lds, ws, dc = [], [], [], [], []
+    for t, col in sources:
+        t2 = t if t.dim() == 2 else t.flatten(1)
+        if t2.stride(-1) != 1 or t2.dtype != torch.float32:
+            t2 = t2.float().contiguous()
+        if not t2.is_cuda or t2.shape[0] != n:
+            raise RuntimeError("gs_pack_cols: every attribute is a device tensor of N rows")
+        if col < 0 or col + t2.shape[1] > dst.shape[1]:
+            raise RuntimeError("gs_pack_cols: destination columns outside dst")
+        keep.append(t2)
+        ps.append(t2.data_ptr())
+        lds.append(t2.stride(0))
+        ws.append(t2.shape[1])
+        dc.append(col)
+    m2 = means if means.stride(-1) == 1 and means.dtype == torch.float32 else means.float().contiguous()
+    k = len(ps)
+    pd, ldd = _rows(dst)
+    call("sfx_gs_pack_cols", n, k, (ctypes.c_void_p * k)(*ps), (ctypes.c_longlong * k)(*lds),
+         (ctypes.c_int * k)(*ws), (ctypes.c_int * k)(*dc), m2.data_ptr(), m2.stride(0), float(grid_resolution), pd,
+         ldd, ptr(grid_out), ptr(grid_max), stream())
+
+
 def grouped_linear(x: Tensor, weight: Tensor, bias: Tensor, groups: int, *, act: int = ACT_NONE,
                    out: Optional[Tensor] = None, a_amax: Optional[Tuple[int, int]] = None,
                    w_amax: Optional[Tuple[int, int]] = None, y_amax: bool = False):

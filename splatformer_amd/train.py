@@ -36,18 +36,12 @@ RENDER_MODES = ("per_view", "batched")
 
 # ---- FeaturePredictor train forward / backward --------------------------------------------------------------
 def refine_train(fp: FeaturePredictor, gs: Dict[str, Tensor], masks, perms=None, group=None):
-    """refine_packed in train mode -> (packed [N, Cin] refined record, tape)."""
+    """refine_packed in train mode -> (packed [N, sum of output widths] refined record, tape)."""
     means = gs["means"]
     dev = means.device
     n = means.shape[0]
-    cin = fp.gs_features_dim
     cb = fp.backbone.output_dim
-    ld = (cb + cin + 3) // 4 * 4
-    h0 = torch.zeros(n, ld, device=dev, dtype=torch.float32)
-    feat = h0[:, cb:cb + cin]
-    grid = torch.empty(n, 3, device=dev, dtype=torch.int32)
-    gmax = torch.zeros(1, device=dev, dtype=torch.int32)
-    ops.gs_pack(gs, feat, float(fp.grid_resolution), grid, gmax)
+    h0, feat, grid, gmax = fp.pack_input(gs)
     depth = int(gmax.item()).bit_length()
     data = {"coord": means, "grid_coord": grid, "offset": [n], "feat": feat, "serialized_depth": depth}
     _, bb_tape = pt.backbone_forward(fp.backbone.backbone, data, masks, perms=perms, out=h0[:, :cb], group=group)
@@ -57,10 +51,16 @@ def refine_train(fp: FeaturePredictor, gs: Dict[str, Tensor], masks, perms=None,
     for wm, bm in mids:
         hs.append(ops.grouped_linear(hs[-1], wm, bm, len(fp.output_features), act=ops.ACT_RELU))
     n_tanh = fp.ch["means"] if fp.output_features[0] == "means" else 0
-    o = torch.empty(n, out_dim, device=dev, dtype=torch.float32)
-    packed = ops.linear(hs[-1], wl, bl, act=ops.ACT_TANH, act_ncols=n_tanh, residual=feat, pre_out=o)
+    if fp.base_wiring:
+        tab = None
+        o = torch.empty(n, out_dim, device=dev, dtype=torch.float32)
+        packed = ops.linear(hs[-1], wl, bl, act=ops.ACT_TANH, act_ncols=n_tanh, residual=feat, pre_out=o)
+    else:  # any other wiring: the per-column epilogue; `o` keeps what its derivative reads
+        tab = fp.col_table(dev)
+        o = ops.linear(hs[-1], wl, bl)
+        packed = ops.col_epilogue(o, tab, h0)
     # the heads' first-layer input is kept only when a head trains (its weight gradient reads it)
-    return packed, dict(bb=bb_tape, hs=hs, o=o, n_tanh=n_tanh, cb=cb,
+    return packed, dict(bb=bb_tape, hs=hs, o=o, n_tanh=n_tanh, cb=cb, tab=tab,
                         x=x if pt.trains(fp.features_outputhead) else None)
 
 
@@ -87,6 +87,14 @@ def scatter_head_grads(fp: FeaturePredictor, dw1: Tensor, db1: Tensor, dmids, dw
         r += c
 
 
+def _epilogue_bwd(tape: dict, d_packed: Tensor, out: Optional[Tensor]) -> Tensor:
+    """d(loss)/d(packed record) -> d(loss)/d(last-layer output): tanh on the leading columns (ptv3_base.gin's
+    wiring), or the column table's derivative."""
+    if tape.get("tab") is None:
+        return tops.act_bwd(d_packed, tape["o"], tops.DACT_TANH_OUT, ncols=tape["n_tanh"], out=out)
+    return tops.col_epilogue_bwd(d_packed, tape["o"], tape["tab"], out=out)
+
+
 def refine_backward(fp: FeaturePredictor, tape: dict, d_packed: Tensor) -> None:
     """d(loss)/d(packed record) -> gradients of every refiner parameter that requires grad (the input attributes
     are not trained)."""
@@ -99,14 +107,13 @@ def refine_backward(fp: FeaturePredictor, tape: dict, d_packed: Tensor) -> None:
     if heads:  # the last layer's weight gradient wants a multiple of 4 output columns: dz in zero-padded rows
         npad = (out_dim + 3) // 4 * 4
         dzp = torch.zeros(n, npad, device=dev, dtype=torch.float32)
-        dz = tops.act_bwd(d_packed.contiguous(), tape["o"], tops.DACT_TANH_OUT, ncols=tape["n_tanh"],
-                          out=dzp[:, :out_dim])
+        dz = _epilogue_bwd(tape, d_packed.contiguous(), dzp[:, :out_dim])
         dwl = torch.zeros(npad, G * W, device=dev, dtype=torch.float32)
         dbl = torch.zeros(npad, device=dev, dtype=torch.float32)
         tops.linear_wgrad(dzp, hs[-1], dwl, dbl)
         dmids = [(torch.zeros_like(wm), torch.zeros_like(bm)) for wm, bm in mids]
     else:
-        dz = tops.act_bwd(d_packed.contiguous(), tape["o"], tops.DACT_TANH_OUT, ncols=tape["n_tanh"])
+        dz = _epilogue_bwd(tape, d_packed.contiguous(), None)
     dh = tops.linear_bwd_data(dz, pt.wt(wl), dact=tops.DACT_RELU, dact_pre=hs[-1])
     for li in reversed(range(len(mids))):
         wm = mids[li][0]

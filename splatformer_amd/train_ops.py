@@ -331,6 +331,20 @@ def act_bwd(dy: Tensor, pre: Tensor, act: int, ncols: int = -1, out: Optional[Te
     return out
 
 
+def col_epilogue_bwd(dy: Tensor, saved: Tensor, tab, out: Optional[Tensor] = None) -> Tensor:
+    """dz = dy * act_c'(saved) per column: the derivative of ptv3_ops.col_epilogue (`saved` = the z it overwrote,
+    `tab` its ptv3_ops.ColTable) -- sfx_col_epilogue_bwd."""
+    M, N = dy.shape
+    if N != tab.n or saved.shape != dy.shape:
+        raise RuntimeError("col_epilogue_bwd: dy, saved and the table must have the same columns")
+    out = torch.empty(M, N, device=dy.device, dtype=torch.float32) if out is None else out
+    pd, ldd = _rows(dy)
+    ps, lds = _rows(saved)
+    po, ldo = _rows(out)
+    call("sfx_col_epilogue_bwd", M, N, pd, ldd, ps, lds, ptr(tab.d_act), po, ldo, stream())
+    return out
+
+
 def drop_mask(n: int, keep: float, seed: int, device) -> Tensor:
     """DropPath keep mask [n]: 1/keep with probability keep, else 0 (sfx_drop_mask, deterministic in seed)."""
     out = torch.empty(n, device=device, dtype=torch.float32)
