@@ -645,25 +645,15 @@ int sfx_rasterize_bwd_nd(int tiles_x, int tiles_y, int block_width, int img_h, i
                          const int* final_idx, const float* v_out, const float* v_out_alpha, float* v_xy,
                          float* v_xy_abs, float* v_conic, float* v_colors, float* v_opacity, void* stream);
 
-/* ---- evaluation post-processing ------------------------------------------------------------------
- * Replaces train.py:104-113 `(x*255).to(torch.uint8)` of prediction (after the gs_utils.py:111
- * clamp(max=1), applied when clamp_pred != 0) and ground truth, feeding utils/metrics.py:89-91 psnr.
- * sums[img*3 + {0,1,2}] = exact sum(p^2), sum(g^2), sum(p*g) of the quantised values;
- * maxes[img*2 + {0,1}] = max(p), max(g) (the metrics.py:26-29 "divide by 255 if max > 1" rule).
- * Images are [num_images, elems_per_image] contiguous f32. */
-int sfx_image_stats_u8(int num_images, long long elems_per_image, const float* pred, const float* gt,
-                       int clamp_pred, unsigned long long* sums, int* maxes, void* stream);
-/* SSIM per image (utils/metrics.py:93-135: 11x11 Gaussian window sigma 1.5, zero padding, C1 = 0.01^2,
- * C2 = 0.03^2, mean of the SSIM map over channels and pixels).  img1/img2: [num_images][height][width][channels]
- * fp32 (HWC, as rendered); window: the 121 fp32 taps of the reference's 2-D window (row-major); out: [num_images].
- * quantize_u8 = 1 evaluates the uint8 images the evaluation loop scores ((x*255) truncated, img1 clamped to <= 1,
- * then /255: train.py:104-113, metrics.py:26-29); 0 uses the values as given. */
-size_t sfx_ssim_workspace_bytes(int num_images, int height, int width, int channels);
-int sfx_ssim(int num_images, int height, int width, int channels, const float* img1, const float* img2,
-             const float* window, int quantize_u8, float* out, void* ws, size_t ws_bytes, void* stream);
-/* (ABI v16, additive) Training image loss and its derivative: per view v,
+/* ---- image quality: the training loss and the evaluation metrics ----------------------------------
+ * (ABI v17 removed the separate uint8-moments entry and the 121-tap SSIM entry with its workspace query: the
+ * moments and the SSIM of the uint8 images are sfx_eval_metrics_u8's, the SSIM of unquantised images is terms[1]
+ * of sfx_image_loss.)
+ * (ABI v16, additive) Training image loss and its derivative: per view v,
  *   loss_v = l1_weight * mean|p - g| + ssim_weight * (1 - SSIM_v),   means over channels * height * width,
- * with the SSIM of sfx_ssim (unquantised).  pred / gt: [num_images][height][width][channels] fp32 (HWC).
+ * with the SSIM of utils/metrics.py:93-135 on the values as given (11x11 Gaussian window sigma 1.5, zero padding,
+ * C1 = 0.01^2, C2 = 0.03^2, mean of the SSIM map over channels and pixels).
+ * pred / gt: [num_images][height][width][channels] fp32 (HWC).
  * window: the 11 fp32 taps of the reference's normalised 1-D Gaussian (utils/metrics.py:93-96); the 2-D window is
  * their outer product, applied separably with fp64 sums.  view_scale: [num_images] on the device, NULL = 1.
  * terms [num_images][4]: mean|p-g|, SSIM mean, mean (p-g)^2, loss_v (not scaled by view_scale).
@@ -679,8 +669,9 @@ int sfx_image_loss(int num_images, int height, int width, int channels, const fl
                    const float* window, float l1_weight, float ssim_weight, const float* view_scale, float* terms,
                    float* d_pred, void* ws, size_t ws_bytes, void* stream);
 /* (ABI v16, additive) Fused evaluation metrics of RGB predictions against RGB or masked RGBA targets: the uint8
- * quantisation, the object mask of a 'real' scene (train.py:104-113, branch gt_imgs.shape[-1] == 4), the integer
- * moments of sfx_image_stats_u8 and the SSIM of sfx_ssim(quantize_u8 = 1), in one pass over pred and gt.
+ * quantisation of train.py:104-113 `(x*255).to(torch.uint8)` (after the gs_utils.py:111 clamp(max=1) when
+ * clamp_pred != 0), the object mask of a 'real' scene (branch gt_imgs.shape[-1] == 4), the integer moments that
+ * feed utils/metrics.py:89-91 psnr and the SSIM of the uint8 images, in one pass over pred and gt.
  * pred: [num_images][height][width][3] fp32.  gt: [num_images][height][width][gt_pixel_stride] fp32, stride 3 or
  * 4; only its first three channels are the target.  mask: NULL (none), or one fp32 per pixel, mask_pixel_stride
  * floats apart: 4 with mask = gt + 3 is the 4th channel of an RGBA target read in place (one 16-byte load per

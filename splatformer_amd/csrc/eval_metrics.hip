@@ -30,73 +30,56 @@
 // The tile's SSIM sum goes to a per-(view, tile) fp64 partial; a second kernel adds a view's partials in a fixed
 // order.  No float atomics: the same inputs give the same bits.  The integer moments use 64-bit integer atomics
 // (one per quantity and workgroup); integer addition is exact in any order.
-#include "common.h"
+#include "image_common.h"
 
 namespace {
 
-constexpr int ET_X = 32, ET_Y = 16, ER = 5, EW = 11;
-constexpr int ES_X = ET_X + 2 * ER, ES_Y = ET_Y + 2 * ER;
+using namespace sfxi;
+
 constexpr int EPITCH = 44;  // bytes per staged halo row: 42 used; groups of 4 columns read 16 bytes from 4 * group
-constexpr int ETHREADS = 256;
-constexpr int EGROUPS = ET_X / 4;
-constexpr double EC1 = 0.01 * 0.01, EC2 = 0.03 * 0.03;
-static_assert(4 * (EGROUPS - 1) + 16 <= EPITCH && ES_X <= EPITCH && EPITCH % 4 == 0, "row pitch");
-static_assert(ET_X * ET_Y == 2 * ETHREADS, "two output pixels per thread");
+constexpr int EGROUPS = TILE_X / 4;
+static_assert(4 * (EGROUPS - 1) + 16 <= EPITCH && HALO_X <= EPITCH && EPITCH % 4 == 0, "row pitch");
+static_assert(TILE_X * TILE_Y == 2 * THREADS, "two output pixels per thread");
 
-// quant_u8 of metrics.hip: torch's float -> uint8 truncation, saturating instead of wrapping
-__device__ __forceinline__ int quant_u8(float x) {
-  const float y = x * 255.f;
-  const int q = (int)y;
-  return q < 0 ? 0 : (q > 255 ? 255 : q);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
+// the reference's order of operations, with a true division
 __device__ __forceinline__ double ssim_value(double mu1, double mu2, double e11, double e22, double e12) {
-  const double mu11 = mu1 * mu1, mu22 = mu2 * mu2, mu12 = mu1 * mu2;
-  return ((2.0 * mu12 + EC1) * (2.0 * (e12 - mu12) + EC2)) /
-         ((mu11 + mu22 + EC1) * ((e11 - mu11) + (e22 - mu22) + EC2));
+  const SsimTerms t = ssim_terms(mu1, mu2, e11, e22, e12);
+  return ((2.0 * t.mu12 + C1) * t.A2) / (t.B1 * t.B2);
 }
 
 // RGBA: gt is [V][H][W][4], 16-byte aligned, and its 4th channel is the mask (gs, mask, ms are not read)
 template <bool RGBA>
-__global__ void __launch_bounds__(ETHREADS) eval_metrics_kernel(int H, int W, const float* __restrict__ pred,
+__global__ void __launch_bounds__(THREADS) eval_metrics_kernel(int H, int W, const float* __restrict__ pred,
                                                                 const float* __restrict__ gt, int gs,
                                                                 const float* __restrict__ mask, int ms,
                                                                 int clamp_pred, const float* __restrict__ taps,
                                                                 unsigned long long* __restrict__ sums,
                                                                 int* __restrict__ maxes,
                                                                 double* __restrict__ partial) {
-  __shared__ __attribute__((aligned(16))) unsigned char sp[3][ES_Y][EPITCH];
-  __shared__ __attribute__((aligned(16))) unsigned char sg[3][ES_Y][EPITCH];
-  __shared__ double hm[5][ES_Y][ET_X];
-  __shared__ double sw[EW];
+  __shared__ __attribute__((aligned(16))) unsigned char sp[3][HALO_Y][EPITCH];
+  __shared__ __attribute__((aligned(16))) unsigned char sg[3][HALO_Y][EPITCH];
+  __shared__ double hm[5][HALO_Y][TILE_X];
+  __shared__ double sw[WIN];
   __shared__ float lut[256];
-  __shared__ double red[ETHREADS / 64];
+  __shared__ double red[THREADS / 64];
   __shared__ unsigned isum[3];
   __shared__ int imax[2];
   const int tid = threadIdx.x;
   const int img = blockIdx.z;
-  const int x0 = blockIdx.x * ET_X - ER, y0 = blockIdx.y * ET_Y - ER;
   const long long img_px = (long long)img * H * W;
 
-  lut[tid] = (float)tid / 255.f;
-  if (tid < EW) sw[tid] = (double)taps[tid];
+  lut[tid] = unquant_u8(tid);
+  if (tid < WIN) sw[tid] = (double)taps[tid];
   if (tid < 3) isum[tid] = 0u;
   if (tid < 2) imax[tid] = 0;
 
   unsigned spp = 0u, sgg = 0u, spg = 0u;
   int mp = 0, mg = 0;
-  for (int i = tid; i < ES_Y * ES_X; i += ETHREADS) {
-    const int yy = i / ES_X, xx = i % ES_X;
-    const int y = y0 + yy, x = x0 + xx;
+  for (int i = tid; i < HALO_Y * HALO_X; i += THREADS) {
+    const HaloPx h = halo_px(i, H, W);
     int qa[3] = {0, 0, 0}, qb[3] = {0, 0, 0};
-    if (y >= 0 && y < H && x >= 0 && x < W) {
-      const long long px = img_px + (long long)y * W + x;
+    if (h.in) {
+      const long long px = img_px + (long long)h.y * W + h.x;
       const float* pp = pred + px * 3;
       float p[3] = {pp[0], pp[1], pp[2]};
       float g[3], m = 1.f;
@@ -124,7 +107,7 @@ __global__ void __launch_bounds__(ETHREADS) eval_metrics_kernel(int H, int W, co
         qa[c] = quant_u8(v);
         qb[c] = quant_u8(g[c]);
       }
-      if (yy >= ER && yy < ER + ET_Y && xx >= ER && xx < ER + ET_X) {  // the tile's own pixels
+      if (h.own) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           spp += (unsigned)(qa[c] * qa[c]);
@@ -137,8 +120,8 @@ __global__ void __launch_bounds__(ETHREADS) eval_metrics_kernel(int H, int W, co
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      sp[c][yy][xx] = (unsigned char)qa[c];
-      sg[c][yy][xx] = (unsigned char)qb[c];
+      sp[c][h.yy][h.xx] = (unsigned char)qa[c];
+      sg[c][h.yy][h.xx] = (unsigned char)qb[c];
     }
   }
   // a workgroup's sums stay below 512 * 3 * 255^2 < 2^27
@@ -159,14 +142,14 @@ __global__ void __launch_bounds__(ETHREADS) eval_metrics_kernel(int H, int W, co
     atomicMax(&imax[1], mg);
   }
 
-  double w[EW];
+  double w[WIN];
 #pragma unroll
-  for (int j = 0; j < EW; ++j) w[j] = sw[j];
-  const int tx = tid % ET_X, ty = 2 * (tid / ET_X);
-  const int ox = blockIdx.x * ET_X + tx, oy = blockIdx.y * ET_Y + ty;
+  for (int j = 0; j < WIN; ++j) w[j] = sw[j];
+  const int tx = tid % TILE_X, ty = 2 * (tid / TILE_X);
+  const int ox = blockIdx.x * TILE_X + tx, oy = blockIdx.y * TILE_Y + ty;
   double sm = 0.0;
   for (int c = 0; c < 3; ++c) {
-    if (tid < ES_Y * EGROUPS) {  // rows: 4 columns x 11 taps from 14 staged values of each image
+    if (tid < HALO_Y * EGROUPS) {  // rows: 4 columns x 11 taps from 14 staged values of each image
       const int yy = tid / EGROUPS, gx = 4 * (tid % EGROUPS);
       const unsigned* ra = reinterpret_cast<const unsigned*>(&sp[c][yy][gx]);  // 4-byte aligned: pitch and gx are
       const unsigned* rb = reinterpret_cast<const unsigned*>(&sg[c][yy][gx]);
@@ -177,13 +160,13 @@ __global__ void __launch_bounds__(ETHREADS) eval_metrics_kernel(int H, int W, co
 #pragma unroll
         for (int k = 0; k < 5; ++k) acc[o][k] = 0.0;
 #pragma unroll
-      for (int j = 0; j < EW + 3; ++j) {
+      for (int j = 0; j < WIN + 3; ++j) {
         const double a = (double)lut[(wa[j >> 2] >> (8 * (j & 3))) & 255u];
         const double b = (double)lut[(wb[j >> 2] >> (8 * (j & 3))) & 255u];
         const double aa = a * a, bb = b * b, ab = a * b;
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
-          if (j - o >= 0 && j - o < EW) {  // resolved at compile time: taps in ascending order for every column
+          if (j - o >= 0 && j - o < WIN) {  // resolved at compile time: taps in ascending order for every column
             const double wt = w[j - o];
             acc[o][0] = fma(wt, a, acc[o][0]);
             acc[o][1] = fma(wt, b, acc[o][1]);
@@ -202,11 +185,11 @@ __global__ void __launch_bounds__(ETHREADS) eval_metrics_kernel(int H, int W, co
     {  // columns: 12 rows of row moments for the pixels (ty, tx) and (ty + 1, tx)
       double c0[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, c1[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-      for (int r = 0; r < EW + 1; ++r) {
+      for (int r = 0; r < WIN + 1; ++r) {
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
           const double v = hm[k][ty + r][tx];
-          if (r < EW) c0[k] = fma(w[r], v, c0[k]);
+          if (r < WIN) c0[k] = fma(w[r], v, c0[k]);
           if (r >= 1) c1[k] = fma(w[r - 1], v, c1[k]);
         }
       }
@@ -222,49 +205,28 @@ __global__ void __launch_bounds__(ETHREADS) eval_metrics_kernel(int H, int W, co
   __syncthreads();
   if (tid == 0) {
     double s = 0.0;
-    for (int i = 0; i < ETHREADS / 64; ++i) s += red[i];
+    for (int i = 0; i < THREADS / 64; ++i) s += red[i];
     const long long tiles = (long long)gridDim.x * gridDim.y;
     partial[(long long)img * tiles + (long long)blockIdx.y * gridDim.x + blockIdx.x] = s;
   }
 }
 
-__global__ void __launch_bounds__(ETHREADS) eval_ssim_reduce_kernel(long long per_view, double denom,
+__global__ void __launch_bounds__(THREADS) eval_ssim_reduce_kernel(long long per_view, double denom,
                                                                     const double* __restrict__ partial,
                                                                     float* __restrict__ out) {
-  __shared__ double red[ETHREADS];
-  double s = 0.0;
-  const double* p = partial + (long long)blockIdx.x * per_view;
-  for (long long i = threadIdx.x; i < per_view; i += ETHREADS) s += p[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = ETHREADS / 2; o >= 1; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = (float)(red[0] / denom);
-}
-
-struct EvalPlan {
-  long long tiles_x, tiles_y, partials;
-};
-
-// false: a size below 1 (num_images below 0), or more than 2^40 pixels (so every index fits a long long with room)
-bool eval_plan(int V, int H, int W, EvalPlan* p) {
-  if (V < 0 || H < 1 || W < 1) return false;
-  if ((double)V * H * W > (double)(1LL << 40)) return false;
-  p->tiles_x = sfx::ceil_div(W, ET_X);
-  p->tiles_y = sfx::ceil_div(H, ET_Y);
-  p->partials = (long long)V * p->tiles_x * p->tiles_y;
-  return true;
+  double s[1];
+  view_reduce<1>(per_view, partial, s);
+  if (threadIdx.x == 0) out[blockIdx.x] = (float)(s[0] / denom);
 }
 
 }  // namespace
 
 extern "C" {
 
+// the plan of a view's pixels: one tile covers all three channels
 size_t sfx_eval_metrics_workspace_bytes(int num_images, int height, int width) {
-  EvalPlan p;
-  if (!eval_plan(num_images, height, width, &p)) return 0;  // sfx_eval_metrics_u8 refuses these sizes
+  ImagePlan p;
+  if (!image_plan(num_images, height, width, 1, &p)) return 0;  // sfx_eval_metrics_u8 refuses these sizes
   return sizeof(double) * (size_t)p.partials;
 }
 
@@ -273,16 +235,16 @@ int sfx_eval_metrics_u8(int num_images, int height, int width, const float* pred
                         const float* window, unsigned long long* sums, int* maxes, float* ssim, void* ws,
                         size_t ws_bytes, void* stream) {
   sfx::clear_error();
-  EvalPlan p;
-  SFX_REQUIRE(eval_plan(num_images, height, width, &p),
+  ImagePlan p;
+  SFX_REQUIRE(image_plan(num_images, height, width, 1, &p),
               "sfx_eval_metrics_u8: bad sizes (%d images of %d x %d; at most 2^40 pixels)", num_images, height, width);
   SFX_REQUIRE(gt_pixel_stride == 3 || gt_pixel_stride == 4,
               "sfx_eval_metrics_u8: gt_pixel_stride must be 3 or 4 (got %d)", gt_pixel_stride);
   SFX_REQUIRE(!mask || mask_pixel_stride == 1 || mask_pixel_stride == 4,
               "sfx_eval_metrics_u8: mask_pixel_stride must be 1 or 4 (got %d)", mask_pixel_stride);
   if (num_images == 0) return SFX_OK;
-  SFX_REQUIRE(num_images <= 65535, "sfx_eval_metrics_u8: at most 65535 images per call (got %d)", num_images);
-  SFX_REQUIRE(p.tiles_y <= 65535, "sfx_eval_metrics_u8: height above %d", 65535 * ET_Y);
+  SFX_REQUIRE(p.grid_z_fits, "sfx_eval_metrics_u8: at most 65535 images per call (got %d)", num_images);
+  SFX_REQUIRE(p.grid_y_fits, "sfx_eval_metrics_u8: height above %d", 65535 * TILE_Y);
   SFX_REQUIRE(pred && gt && window && sums && maxes && ssim && ws, "sfx_eval_metrics_u8: null buffer");
   SFX_REQUIRE((uintptr_t)ws % 8 == 0, "sfx_eval_metrics_u8: workspace must be 8-byte aligned");
   SFX_REQUIRE(ws_bytes >= sizeof(double) * (size_t)p.partials, "sfx_eval_metrics_u8: workspace too small");
@@ -297,13 +259,13 @@ int sfx_eval_metrics_u8(int num_images, int height, int width, const float* pred
   // the mask as the 4th channel of an aligned RGBA target: one 16-byte load per pixel
   const bool rgba = gt_pixel_stride == 4 && mask == gt + 3 && mask_pixel_stride == 4 && (uintptr_t)gt % 16 == 0;
   if (rgba)
-    eval_metrics_kernel<true><<<grid, ETHREADS, 0, st>>>(height, width, pred, gt, 4, mask, 4, clamp_pred, window,
+    eval_metrics_kernel<true><<<grid, THREADS, 0, st>>>(height, width, pred, gt, 4, mask, 4, clamp_pred, window,
                                                          sums, maxes, partial);
   else
-    eval_metrics_kernel<false><<<grid, ETHREADS, 0, st>>>(height, width, pred, gt, gt_pixel_stride, mask,
+    eval_metrics_kernel<false><<<grid, THREADS, 0, st>>>(height, width, pred, gt, gt_pixel_stride, mask,
                                                           mask_pixel_stride, clamp_pred, window, sums, maxes,
                                                           partial);
-  eval_ssim_reduce_kernel<<<num_images, ETHREADS, 0, st>>>(p.tiles_x * p.tiles_y, 3.0 * height * width, partial,
+  eval_ssim_reduce_kernel<<<num_images, THREADS, 0, st>>>(p.tiles_x * p.tiles_y, 3.0 * height * width, partial,
                                                            ssim);
   return sfx::check_launch("sfx_eval_metrics_u8");
 }

@@ -22,98 +22,74 @@
 // background) e11 - mu1^2 cancels seven digits and the three terms of the derivative cancel three more, which an
 // fp32 sum does not survive; the maps themselves are stored as fp32.  VALU + LDS only, no atomics: every sum
 // has one fixed order, so two calls give the same bits.
-#include "common.h"
+#include "image_common.h"
 
 namespace {
 
-constexpr int LT_X = 32, LT_Y = 16, LR = 5, LW = 11;
-constexpr int LS_X = LT_X + 2 * LR, LS_Y = LT_Y + 2 * LR;
-constexpr int LTHREADS = 256;
-constexpr double LC1 = 0.01 * 0.01, LC2 = 0.03 * 0.03;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using namespace sfxi;
 
 // maps != NULL: also write the derivative maps (plane stride `plane` elements) for pass B.  One instantiation, so
 // the terms have the same bits with and without a gradient.
-__global__ void __launch_bounds__(LTHREADS) loss_moments_kernel(int H, int W, int C, const float* __restrict__ pred,
+__global__ void __launch_bounds__(THREADS) loss_moments_kernel(int H, int W, int C, const float* __restrict__ pred,
                                                                 const float* __restrict__ gt,
                                                                 const float* __restrict__ taps,
                                                                 double* __restrict__ partial,
                                                                 float* __restrict__ maps, long long plane) {
-  __shared__ float sp[LS_Y][LS_X + 1], sg[LS_Y][LS_X + 1];
-  __shared__ double hm[5][LS_Y][LT_X];
-  __shared__ double sw[LW];
-  __shared__ double red[LTHREADS / 64][3];
+  __shared__ float sp[HALO_Y][HALO_X + 1], sg[HALO_Y][HALO_X + 1];
+  __shared__ double hm[5][HALO_Y][TILE_X];
+  __shared__ double sw[WIN];
+  __shared__ double red[THREADS / 64][3];
   const int img = blockIdx.z / C, c = blockIdx.z % C;
-  const int x0 = blockIdx.x * LT_X - LR, y0 = blockIdx.y * LT_Y - LR;
   const long long base = (long long)img * H * W * C;
   double l1 = 0.0, l2 = 0.0, sm = 0.0;
-  for (int i = threadIdx.x; i < LS_Y * LS_X; i += LTHREADS) {
-    const int yy = i / LS_X, xx = i % LS_X;
-    const int y = y0 + yy, x = x0 + xx;
-    const bool in = y >= 0 && y < H && x >= 0 && x < W;
+  for (int i = threadIdx.x; i < HALO_Y * HALO_X; i += THREADS) {
+    const HaloPx h = halo_px(i, H, W);
     float a = 0.f, b = 0.f;
-    if (in) {
-      const long long o = base + ((long long)y * W + x) * C + c;
+    if (h.in) {
+      const long long o = base + ((long long)h.y * W + h.x) * C + c;
       a = pred[o];
       b = gt[o];
-      if (yy >= LR && yy < LR + LT_Y && xx >= LR && xx < LR + LT_X) {  // the tile's own pixels
+      if (h.own) {
         const double d = (double)a - (double)b;
         l1 += fabs(d);
         l2 += d * d;
       }
     }
-    sp[yy][xx] = a;
-    sg[yy][xx] = b;
+    sp[h.yy][h.xx] = a;
+    sg[h.yy][h.xx] = b;
   }
-  if (threadIdx.x < LW) sw[threadIdx.x] = (double)taps[threadIdx.x];
+  if (threadIdx.x < WIN) sw[threadIdx.x] = (double)taps[threadIdx.x];
   __syncthreads();
-  for (int i = threadIdx.x; i < LS_Y * LT_X; i += LTHREADS) {  // rows: 11 columns
-    const int yy = i / LT_X, x = i % LT_X;
-    double m1 = 0.0, m2 = 0.0, s11 = 0.0, s22 = 0.0, s12 = 0.0;
+  for (int i = threadIdx.x; i < HALO_Y * TILE_X; i += THREADS) {  // rows: w*p, w*g, w*p^2, w*g^2, w*pg
+    const int yy = i / TILE_X, x = i % TILE_X;
+    double r[5];
+    window_sum<5>(sw, r, [&](int j, double* v) {
+      const double a = sp[yy][x + j], b = sg[yy][x + j];
+      v[0] = a, v[1] = b, v[2] = a * a, v[3] = b * b, v[4] = a * b;
+    });
 #pragma unroll
-    for (int j = 0; j < LW; ++j) {
-      const double w = sw[j], a = sp[yy][x + j], b = sg[yy][x + j];
-      m1 = fma(w, a, m1);
-      m2 = fma(w, b, m2);
-      s11 = fma(w, a * a, s11);
-      s22 = fma(w, b * b, s22);
-      s12 = fma(w, a * b, s12);
-    }
-    hm[0][yy][x] = m1;
-    hm[1][yy][x] = m2;
-    hm[2][yy][x] = s11;
-    hm[3][yy][x] = s22;
-    hm[4][yy][x] = s12;
+    for (int k = 0; k < 5; ++k) hm[k][yy][x] = r[k];
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < LT_Y * LT_X; i += LTHREADS) {  // columns: 11 rows
-    const int ty = i / LT_X, tx = i % LT_X;
-    const int y = blockIdx.y * LT_Y + ty, x = blockIdx.x * LT_X + tx;
+  for (int i = threadIdx.x; i < TILE_Y * TILE_X; i += THREADS) {  // columns: mu1, mu2, e11, e22, e12
+    const int ty = i / TILE_X, tx = i % TILE_X;
+    const int y = blockIdx.y * TILE_Y + ty, x = blockIdx.x * TILE_X + tx;
     if (y >= H || x >= W) continue;
-    double mu1 = 0.0, mu2 = 0.0, e11 = 0.0, e22 = 0.0, e12 = 0.0;
+    double e[5];
+    window_sum<5>(sw, e, [&](int j, double* v) {
 #pragma unroll
-    for (int j = 0; j < LW; ++j) {
-      const double w = sw[j];
-      mu1 = fma(w, hm[0][ty + j][tx], mu1);
-      mu2 = fma(w, hm[1][ty + j][tx], mu2);
-      e11 = fma(w, hm[2][ty + j][tx], e11);
-      e22 = fma(w, hm[3][ty + j][tx], e22);
-      e12 = fma(w, hm[4][ty + j][tx], e12);
-    }
-    const double A1 = 2.0 * mu1 * mu2 + LC1, A2 = 2.0 * (e12 - mu1 * mu2) + LC2;
-    const double B1 = mu1 * mu1 + mu2 * mu2 + LC1, B2 = (e11 - mu1 * mu1) + (e22 - mu2 * mu2) + LC2;
-    const double rb = 1.0 / (B1 * B2);
-    const double m = A1 * A2 * rb;
+      for (int k = 0; k < 5; ++k) v[k] = hm[k][ty + j][tx];
+    });
+    const double mu1 = e[0], mu2 = e[1];
+    const SsimTerms t = ssim_terms(mu1, mu2, e[2], e[3], e[4]);
+    const double A1 = 2.0 * mu1 * mu2 + C1;
+    const double rb = 1.0 / (t.B1 * t.B2);
+    const double m = A1 * t.A2 * rb;
     sm += m;
     if (maps) {
       const long long o = base + ((long long)y * W + x) * C + c;
-      maps[o] = (float)(2.0 * mu2 * (A2 - A1) * rb - 2.0 * mu1 * m / B1 + 2.0 * mu1 * m / B2);
-      maps[plane + o] = (float)(-m / B2);
+      maps[o] = (float)(2.0 * mu2 * (t.A2 - A1) * rb - 2.0 * mu1 * m / t.B1 + 2.0 * mu1 * m / t.B2);
+      maps[plane + o] = (float)(-m / t.B2);
       maps[2 * plane + o] = (float)(2.0 * A1 * rb);
     }
   }
@@ -128,7 +104,7 @@ __global__ void __launch_bounds__(LTHREADS) loss_moments_kernel(int H, int W, in
   __syncthreads();
   if (threadIdx.x < 3) {
     double s = 0.0;
-    for (int w = 0; w < LTHREADS / 64; ++w) s += red[w][threadIdx.x];
+    for (int w = 0; w < THREADS / 64; ++w) s += red[w][threadIdx.x];
     const long long tiles = (long long)gridDim.x * gridDim.y;
     const long long t = (long long)blockIdx.z * tiles + (long long)blockIdx.y * gridDim.x + blockIdx.x;
     partial[t * 3 + threadIdx.x] = s;
@@ -136,26 +112,13 @@ __global__ void __launch_bounds__(LTHREADS) loss_moments_kernel(int H, int W, in
 }
 
 // terms[v] = mean|p-g|, SSIM mean, mean (p-g)^2, l1_weight * [0] + ssim_weight * (1 - [1])
-__global__ void __launch_bounds__(LTHREADS) loss_reduce_kernel(long long per_view, double denom, float l1_weight,
+__global__ void __launch_bounds__(THREADS) loss_reduce_kernel(long long per_view, double denom, float l1_weight,
                                                                float ssim_weight, const double* __restrict__ partial,
                                                                float* __restrict__ terms) {
-  __shared__ double red[3][LTHREADS];
-  double s[3] = {0.0, 0.0, 0.0};
-  const double* p = partial + (long long)blockIdx.x * per_view * 3;
-  for (long long i = threadIdx.x; i < per_view; i += LTHREADS) {
-    s[0] += p[i * 3 + 0];
-    s[1] += p[i * 3 + 1];
-    s[2] += p[i * 3 + 2];
-  }
-  for (int k = 0; k < 3; ++k) red[k][threadIdx.x] = s[k];
-  __syncthreads();
-  for (int o = LTHREADS / 2; o >= 1; o >>= 1) {
-    if (threadIdx.x < o)
-      for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
-    __syncthreads();
-  }
+  double s[3];
+  view_reduce<3>(per_view, partial, s);
   if (threadIdx.x == 0) {
-    const double l1 = red[0][0] / denom, mse = red[1][0] / denom, ssim = red[2][0] / denom;
+    const double l1 = s[0] / denom, mse = s[1] / denom, ssim = s[2] / denom;
     float* t = terms + (long long)blockIdx.x * 4;
     t[0] = (float)l1;
     t[1] = (float)ssim;
@@ -166,85 +129,60 @@ __global__ void __launch_bounds__(LTHREADS) loss_reduce_kernel(long long per_vie
 
 // SSIM: convolve the three maps and combine; otherwise the L1 sign term alone (the maps are not read)
 template <bool SSIM>
-__global__ void __launch_bounds__(LTHREADS) loss_grad_kernel(int H, int W, int C, const float* __restrict__ pred,
+__global__ void __launch_bounds__(THREADS) loss_grad_kernel(int H, int W, int C, const float* __restrict__ pred,
                                                              const float* __restrict__ gt,
                                                              const float* __restrict__ taps,
                                                              const float* __restrict__ maps, long long plane,
                                                              float l1_weight, float ssim_weight,
                                                              const float* __restrict__ view_scale, double denom,
                                                              float* __restrict__ d_pred) {
-  __shared__ float sd[SSIM ? 3 : 1][LS_Y][LS_X + 1];
-  __shared__ double hd[SSIM ? 3 : 1][LS_Y][LT_X];
-  __shared__ double sw[LW];
+  __shared__ float sd[SSIM ? 3 : 1][HALO_Y][HALO_X + 1];
+  __shared__ double hd[SSIM ? 3 : 1][HALO_Y][TILE_X];
+  __shared__ double sw[WIN];
   const int img = blockIdx.z / C, c = blockIdx.z % C;
   const long long base = (long long)img * H * W * C;
   const double vs = view_scale ? (double)view_scale[img] : 1.0;
   const double cl1 = (double)l1_weight * vs / denom;  // sign's coefficient, rounded to fp32 once at the store
   const double cs = -(double)ssim_weight * vs / denom;
   if (SSIM) {
-    const int x0 = blockIdx.x * LT_X - LR, y0 = blockIdx.y * LT_Y - LR;
-    for (int i = threadIdx.x; i < LS_Y * LS_X; i += LTHREADS) {
-      const int yy = i / LS_X, xx = i % LS_X;
-      const int y = y0 + yy, x = x0 + xx;
-      const bool in = y >= 0 && y < H && x >= 0 && x < W;
-      const long long o = base + ((long long)y * W + x) * C + c;
+    for (int i = threadIdx.x; i < HALO_Y * HALO_X; i += THREADS) {
+      const HaloPx h = halo_px(i, H, W);
+      const long long o = base + ((long long)h.y * W + h.x) * C + c;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) sd[k][yy][xx] = in ? maps[k * plane + o] : 0.f;
+      for (int k = 0; k < 3; ++k) sd[k][h.yy][h.xx] = h.in ? maps[k * plane + o] : 0.f;
     }
-    if (threadIdx.x < LW) sw[threadIdx.x] = (double)taps[threadIdx.x];
+    if (threadIdx.x < WIN) sw[threadIdx.x] = (double)taps[threadIdx.x];
     __syncthreads();
-    for (int i = threadIdx.x; i < LS_Y * LT_X; i += LTHREADS) {
-      const int yy = i / LT_X, x = i % LT_X;
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int i = threadIdx.x; i < HALO_Y * TILE_X; i += THREADS) {
+      const int yy = i / TILE_X, x = i % TILE_X;
+      double r[3];
+      window_sum<3>(sw, r, [&](int j, double* v) {
 #pragma unroll
-      for (int j = 0; j < LW; ++j) {
-        const double w = sw[j];
-        a0 = fma(w, (double)sd[0][yy][x + j], a0);
-        a1 = fma(w, (double)sd[1][yy][x + j], a1);
-        a2 = fma(w, (double)sd[2][yy][x + j], a2);
-      }
-      hd[0][yy][x] = a0;
-      hd[1][yy][x] = a1;
-      hd[2][yy][x] = a2;
+        for (int k = 0; k < 3; ++k) v[k] = (double)sd[k][yy][x + j];
+      });
+#pragma unroll
+      for (int k = 0; k < 3; ++k) hd[k][yy][x] = r[k];
     }
     __syncthreads();
   }
-  for (int i = threadIdx.x; i < LT_Y * LT_X; i += LTHREADS) {
-    const int ty = i / LT_X, tx = i % LT_X;
-    const int y = blockIdx.y * LT_Y + ty, x = blockIdx.x * LT_X + tx;
+  for (int i = threadIdx.x; i < TILE_Y * TILE_X; i += THREADS) {
+    const int ty = i / TILE_X, tx = i % TILE_X;
+    const int y = blockIdx.y * TILE_Y + ty, x = blockIdx.x * TILE_X + tx;
     if (y >= H || x >= W) continue;
     const long long o = base + ((long long)y * W + x) * C + c;
     const double p = pred[o], g = gt[o];
     const double sgn = p > g ? 1.0 : (p < g ? -1.0 : 0.0);  // sign(0) = 0 (torch's abs backward)
     double out = cl1 * sgn;
     if (SSIM) {
-      double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+      double s[3];
+      window_sum<3>(sw, s, [&](int j, double* v) {
 #pragma unroll
-      for (int j = 0; j < LW; ++j) {
-        const double w = sw[j];
-        c0 = fma(w, hd[0][ty + j][tx], c0);
-        c1 = fma(w, hd[1][ty + j][tx], c1);
-        c2 = fma(w, hd[2][ty + j][tx], c2);
-      }
-      out += cs * (c0 + 2.0 * p * c1 + g * c2);
+        for (int k = 0; k < 3; ++k) v[k] = hd[k][ty + j][tx];
+      });
+      out += cs * (s[0] + 2.0 * p * s[1] + g * s[2]);
     }
     d_pred[o] = (float)out;
   }
-}
-
-struct LossPlan {
-  long long tiles_x, tiles_y, elems, partials;
-};
-
-// false: a non-positive size, or more than 2^40 elements (so every index below fits a long long with room)
-bool loss_plan(int V, int H, int W, int C, LossPlan* p) {
-  if (V < 0 || H <= 0 || W <= 0 || C <= 0) return false;
-  if ((double)V * H * W * C > (double)(1LL << 40)) return false;
-  p->tiles_x = sfx::ceil_div(W, LT_X);
-  p->tiles_y = sfx::ceil_div(H, LT_Y);
-  p->elems = (long long)V * H * W * C;
-  p->partials = (long long)V * C * p->tiles_x * p->tiles_y;
-  return true;
 }
 
 bool overlaps(const float* a, const float* b, long long n) {
@@ -257,8 +195,8 @@ bool overlaps(const float* a, const float* b, long long n) {
 extern "C" {
 
 size_t sfx_image_loss_workspace_bytes(int num_images, int height, int width, int channels) {
-  LossPlan p;
-  if (!loss_plan(num_images, height, width, channels, &p)) return 0;  // sfx_image_loss refuses these sizes
+  ImagePlan p;
+  if (!image_plan(num_images, height, width, channels, &p)) return 0;  // sfx_image_loss refuses these sizes
   return sizeof(double) * 3 * (size_t)p.partials + sizeof(float) * 3 * (size_t)p.elems;
 }
 
@@ -266,15 +204,15 @@ int sfx_image_loss(int num_images, int height, int width, int channels, const fl
                    const float* window, float l1_weight, float ssim_weight, const float* view_scale, float* terms,
                    float* d_pred, void* ws, size_t ws_bytes, void* stream) {
   sfx::clear_error();
-  LossPlan p;
-  SFX_REQUIRE(loss_plan(num_images, height, width, channels, &p),
+  ImagePlan p;
+  SFX_REQUIRE(image_plan(num_images, height, width, channels, &p),
               "sfx_image_loss: bad sizes (%d images of %d x %d x %d; at most 2^40 elements)", num_images, height, width,
               channels);
   SFX_REQUIRE(l1_weight >= 0.f && ssim_weight >= 0.f, "sfx_image_loss: negative (or NaN) loss weight");
   if (num_images == 0) return SFX_OK;
-  SFX_REQUIRE((long long)num_images * channels <= 65535,
-              "sfx_image_loss: at most 65535 view-channels per call (got %lld)", (long long)num_images * channels);
-  SFX_REQUIRE(p.tiles_y <= 65535, "sfx_image_loss: height above %d", 65535 * LT_Y);
+  SFX_REQUIRE(p.grid_z_fits, "sfx_image_loss: at most 65535 view-channels per call (got %lld)",
+              (long long)num_images * channels);
+  SFX_REQUIRE(p.grid_y_fits, "sfx_image_loss: height above %d", 65535 * TILE_Y);
   SFX_REQUIRE(pred && gt && window && terms && ws, "sfx_image_loss: null buffer");
   SFX_REQUIRE((uintptr_t)ws % 8 == 0, "sfx_image_loss: workspace must be 8-byte aligned");
   // forward only: the tile sums alone; with d_pred the three derivative maps as well (the query's size)
@@ -289,16 +227,16 @@ int sfx_image_loss(int num_images, int height, int width, int channels, const fl
   float* maps = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + part_bytes);
   const dim3 grid((unsigned)p.tiles_x, (unsigned)p.tiles_y, (unsigned)(num_images * channels));
   const double denom = (double)channels * height * width;
-  loss_moments_kernel<<<grid, LTHREADS, 0, st>>>(height, width, channels, pred, gt, window, partial,
+  loss_moments_kernel<<<grid, THREADS, 0, st>>>(height, width, channels, pred, gt, window, partial,
                                                  grad_ssim ? maps : nullptr, p.elems);
-  loss_reduce_kernel<<<num_images, LTHREADS, 0, st>>>((long long)channels * p.tiles_x * p.tiles_y, denom, l1_weight,
+  loss_reduce_kernel<<<num_images, THREADS, 0, st>>>((long long)channels * p.tiles_x * p.tiles_y, denom, l1_weight,
                                                       ssim_weight, partial, terms);
   if (d_pred) {
     if (grad_ssim)
-      loss_grad_kernel<true><<<grid, LTHREADS, 0, st>>>(height, width, channels, pred, gt, window, maps, p.elems,
+      loss_grad_kernel<true><<<grid, THREADS, 0, st>>>(height, width, channels, pred, gt, window, maps, p.elems,
                                                         l1_weight, ssim_weight, view_scale, denom, d_pred);
     else
-      loss_grad_kernel<false><<<grid, LTHREADS, 0, st>>>(height, width, channels, pred, gt, window, nullptr, 0,
+      loss_grad_kernel<false><<<grid, THREADS, 0, st>>>(height, width, channels, pred, gt, window, nullptr, 0,
                                                          l1_weight, ssim_weight, view_scale, denom, d_pred);
   }
   return sfx::check_launch("sfx_image_loss");

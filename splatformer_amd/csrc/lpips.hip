@@ -26,6 +26,7 @@
 // Every floating-point sum has one fixed order (MFMA chains, in-wave butterflies, one thread's sequential loops):
 // two calls give equal bits.  There are no floating-point atomics.
 #include "gemm_common.h"
+#include "image_common.h"
 
 namespace {
 
@@ -379,12 +380,7 @@ __global__ void __launch_bounds__(256) lpips_input_kernel(long long total, const
   const int c = (int)(idx % 3);
   float p = x[idx];
   if (mask) p = p * mask[idx / 3];  // its own rounding, before the * 255.f (sfx_eval_metrics_u8)
-  if (quantize) {
-    const float q = p * 255.f;
-    int i = (int)q;
-    i = i < 0 ? 0 : (i > 255 ? 255 : i);
-    p = (float)i / 255.f;
-  }
+  if (quantize) p = sfxi::unquant_u8(sfxi::quant_u8(p));
   u[idx] = ((2.f * p - 1.f) - in_shift(c)) / in_scale(c);
 }
 

@@ -9,8 +9,8 @@ column of the reference's eval.csv, LPIPS (utils/metrics.py:13-17), is computed 
 
 Masked branch (train.py:104-109, 'real' scenes): a target with a fourth channel (dataset/GS.py:128-151, the
 object mask appended by scene_io.read_image) takes `pred = pred * mask` before the uint8 truncation; the target
-is used as composited and the metrics run over all pixels.  That branch is one fused kernel
-(metrics.eval_metrics_u8) reading the RGBA target in place; 3-channel targets keep the two kernels they had.
+is used as composited and the metrics run over all pixels.  Both kinds of target are scored by one fused kernel
+(metrics.eval_metrics_u8), which reads an RGBA target in place.
 The per-scene, per-image record (MetricComputer.results_dict, utils/metrics.py:48, written as
 metrics.rank{r}.json by :82-84 / train.py:165) and `compare_with_input` (train.py:127-136, :184-189) are
 optional outputs of the same loop.
@@ -24,17 +24,14 @@ import torch
 
 from . import _lib, dist
 from .gs_render import rasterize_gaussians_to_multiimgs
-from .metrics import eval_metrics_u8, image_stats_u8, psnr_from_stats, ssim
+from .metrics import eval_metrics_u8
 
 
 def _score(pred: torch.Tensor, gt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Per-image (psnr, ssim), float64 on the host, of rendered `pred` [V,H,W,3] against gt [V,H,W,3 or 4]."""
-    if gt.shape[-1] == 4:  # train.py:104-109: mask the prediction, one fused pass over the RGBA target
-        m = eval_metrics_u8(pred, gt, clamp_pred=False)  # rgbs are already clamped (gs_utils.py:111)
-        return m["psnr"], m["ssim"].double().cpu()
-    sums, maxes = image_stats_u8(pred, gt, clamp_pred=False)  # rgbs are already clamped (gs_utils.py:111)
-    psnr = psnr_from_stats(sums, maxes, pred[0].numel())
-    return psnr, ssim(pred, gt, quantize_u8=True).double().cpu()
+    """Per-image (psnr, ssim), float64 on the host, of rendered `pred` [V,H,W,3] against gt [V,H,W,3 or 4]: one
+    fused pass; a 4th channel of gt is the mask that multiplies the prediction (train.py:104-109)."""
+    m = eval_metrics_u8(pred, gt, clamp_pred=False)  # rgbs are already clamped (gs_utils.py:111)
+    return m["psnr"], m["ssim"].double().cpu()
 
 
 def _lpips(net, pred: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:

@@ -17,12 +17,9 @@ from torch import Tensor
 
 from . import _lib
 from ._lib import call, ptr, stream
-from .metrics import gaussian_taps
+from .metrics import device_taps
 
 Images = Union[Tensor, Sequence[Tensor]]
-
-
-_TAPS: dict = {}
 
 
 def _stacked(x: Images) -> Tensor:
@@ -50,9 +47,7 @@ def _run(pred: Tensor, gt: Tensor, l1_weight: float, ssim_weight: float, view_sc
         if view_scale.shape != (V,):
             raise ValueError(f"view_scale: expected [{V}], got {tuple(view_scale.shape)}")
         view_scale = view_scale.detach().to(device=dev, dtype=torch.float32).contiguous()
-    taps = _TAPS.get(dev)
-    if taps is None:
-        taps = _TAPS[dev] = gaussian_taps().to(dev)
+    taps = device_taps(dev)
     grad_ssim = want_grad and ssim_weight > 0.0
     nbytes = int(_lib.fn("sfx_image_loss_workspace_bytes")(V, H, W, C))
     if not grad_ssim:  # tile sums only (include/sfx.h): no room for the derivative maps
@@ -63,6 +58,11 @@ def _run(pred: Tensor, gt: Tensor, l1_weight: float, ssim_weight: float, view_sc
     call("sfx_image_loss", V, H, W, C, ptr(p), ptr(g), ptr(taps), float(l1_weight), float(ssim_weight),
          ptr(view_scale), ptr(terms), ptr(d_pred), ptr(ws), ws.numel(), stream())
     return terms, d_pred
+
+
+def image_loss_terms(pred: Images, gt: Images, l1_weight: float = 1.0, ssim_weight: float = 0.0) -> Tensor:
+    """Forward only: the terms [V,4] of image_loss_and_grad, no derivative (metrics.ssim is terms[:, 1])."""
+    return _run(_stacked(pred), _stacked(gt), l1_weight, ssim_weight, None, False)[0]
 
 
 def image_loss_and_grad(pred: Images, gt: Images, l1_weight: float = 1.0, ssim_weight: float = 0.0,

@@ -7,38 +7,35 @@
   the whole [V,H,W,3] batch);
 - utils/metrics.py:89-91: psnr = 20 log10(1 / sqrt(mse)) per image.
 
-The quantisation and the per-image integer moments run in one HIP kernel (sfx_image_stats_u8); mse is
-formed on the host from the exact integer sums.  Divergence (documented): when a batch's max is <= 1 and
-the OTHER batch's is too, the reference subtracts two uint8 tensors (wrap-around) and then fails in
-`.mean()` on a Byte tensor; here the values are used unscaled instead.
-
 `eval_metrics_u8(pred, gt, mask)` is the same contract with the object mask of a 'real' scene (train.py:104-109:
-the prediction alone is multiplied by the mask before the truncation) and the SSIM of the same uint8 images, from
-one fused kernel (sfx_eval_metrics_u8) that reads an RGBA target in place.
+the prediction alone is multiplied by the mask before the truncation) and the SSIM of the same uint8 images.  Both
+come from one fused HIP kernel (sfx_eval_metrics_u8) that reads an RGBA target in place: the quantisation, the
+per-image exact integer moments and the SSIM; mse is formed on the host from the integer sums.  `image_stats_u8`,
+`psnr_u8` and `ssim(quantize_u8=True)` are that kernel without a mask; `ssim` of unquantised images is the SSIM term
+of the training loss's kernel (sfx_image_loss, forward only).
+
+Divergence (documented): when a batch's max is <= 1 and the OTHER batch's is too, the reference subtracts two uint8
+tensors (wrap-around) and then fails in `.mean()` on a Byte tensor; here the values are used unscaled instead.
 """
 from __future__ import annotations
 
-import torch
-
 import math
+
+import torch
 
 from . import _lib
 from ._lib import call, ptr, stream
 
 
+def _same_rgb(what: str, pred: torch.Tensor, gt: torch.Tensor) -> None:
+    if pred.shape != gt.shape or pred.dim() != 4 or pred.shape[-1] != 3:
+        raise ValueError(f"{what}: expected two equal [V,H,W,3] tensors, got {tuple(pred.shape)}, {tuple(gt.shape)}")
+
+
 def image_stats_u8(pred: torch.Tensor, gt: torch.Tensor, clamp_pred: bool = True):
-    """Per-image exact integer moments of the quantised images: sums [V,3] (p², g², pg), maxes [V,2]."""
-    _lib.require_gpu(pred)
-    if pred.shape != gt.shape:
-        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ")
-    V = pred.shape[0]
-    pred = pred.float().contiguous()
-    gt = gt.float().contiguous()
-    elems = pred.numel() // max(V, 1)
-    sums = torch.empty(V, 3, device=pred.device, dtype=torch.int64)
-    maxes = torch.empty(V, 2, device=pred.device, dtype=torch.int32)
-    call("sfx_image_stats_u8", V, elems, ptr(pred), ptr(gt), 1 if clamp_pred else 0, ptr(sums), ptr(maxes),
-         stream())
+    """Per-image exact integer moments of the quantised [V,H,W,3] images: sums [V,3] (p², g², pg), maxes [V,2]."""
+    _same_rgb("image_stats_u8", pred, gt)
+    sums, maxes, _ = eval_stats_u8(pred, gt, clamp_pred=clamp_pred)
     return sums, maxes
 
 
@@ -72,34 +69,31 @@ def ssim_window(window_size: int = 11, sigma: float = 1.5) -> torch.Tensor:
     return g.mm(g.t()).float()
 
 
-_WIN = {}
+_TAPS = {}
+
+
+def device_taps(dev: torch.device) -> torch.Tensor:
+    """gaussian_taps() on `dev`, uploaded once: the `window` argument of sfx_eval_metrics_u8 and sfx_image_loss."""
+    taps = _TAPS.get(dev)
+    if taps is None:
+        taps = _TAPS[dev] = gaussian_taps().to(dev)
+    return taps
 
 
 def ssim(img1: torch.Tensor, img2: torch.Tensor, quantize_u8: bool = False) -> torch.Tensor:
     """[V,H,W,C] images (HWC) -> SSIM per image [V] (float32 on the device), = MetricComputer's
-    `ssim(x.permute(0,3,1,2), ..., window_size=11, size_average=False)` (metrics.py:15, :103-135).
-    quantize_u8: score the uint8 images of the evaluation loop (truncation, img1 clamped to <= 1, /255) --
-    the batch-max rule of metrics.py:26-29 is taken as dividing (it differs only for images whose largest
-    uint8 value is <= 1)."""
-    _lib.require_gpu(img1)
+    `ssim(x.permute(0,3,1,2), ..., window_size=11, size_average=False)` (metrics.py:15, :103-135): the SSIM term of
+    a forward-only sfx_image_loss call.
+    quantize_u8: score the uint8 images of the evaluation loop (truncation, img1 clamped to <= 1, /255) -- C must be
+    3, the SSIM of eval_stats_u8; the batch-max rule of metrics.py:26-29 is taken as dividing (it differs only for
+    images whose largest uint8 value is <= 1)."""
+    if quantize_u8:
+        _same_rgb("ssim(quantize_u8=True)", img1, img2)
+        return eval_stats_u8(img1, img2, clamp_pred=True)[2]
     if img1.shape != img2.shape or img1.dim() != 4:
         raise ValueError(f"ssim: expected two equal [V,H,W,C] tensors, got {tuple(img1.shape)}, {tuple(img2.shape)}")
-    V, H, W, C = img1.shape
-    a = img1.float().contiguous()
-    b = img2.float().contiguous()
-    dev = a.device
-    win = _WIN.get(dev)
-    if win is None:
-        win = _WIN[dev] = ssim_window().reshape(-1).to(dev)
-    nbytes = _lib.fn("sfx_ssim_workspace_bytes")(V, H, W, C)
-    ws = torch.empty(max(int(nbytes), 4), dtype=torch.uint8, device=dev)
-    out = torch.empty(V, dtype=torch.float32, device=dev)
-    call("sfx_ssim", V, H, W, C, ptr(a), ptr(b), ptr(win), 1 if quantize_u8 else 0, ptr(out), ptr(ws), ws.numel(),
-         stream())
-    return out
-
-
-_TAPS = {}
+    from .losses import image_loss_terms  # losses imports this module's taps
+    return image_loss_terms(img1, img2)[:, 1].contiguous()
 
 
 def eval_stats_u8(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor | None = None,
@@ -127,9 +121,7 @@ def eval_stats_u8(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor | Non
     else:
         mptr, ms = None, 0
     dev = pred.device
-    taps = _TAPS.get(dev)
-    if taps is None:
-        taps = _TAPS[dev] = gaussian_taps().to(dev)
+    taps = device_taps(dev)
     sums = torch.empty(V, 3, device=dev, dtype=torch.int64)
     maxes = torch.empty(V, 2, device=dev, dtype=torch.int32)
     out = torch.empty(V, dtype=torch.float32, device=dev)

@@ -31,7 +31,7 @@ def test_signatures_are_bound_from_the_header():
     assert L.SIGNATURES["sfx_eval_metrics_u8"] == [I, I, I, Pv, Pv, I, Pv, I, I, Pv, Pv, Pv, Pv, Pv, Z, Pv]
     lib = _lib()
     assert lib.sfx_eval_metrics_workspace_bytes.restype is Z
-    assert lib.sfx_abi_version() == 16
+    assert lib.sfx_abi_version() == 17
 
 
 @pytest.mark.parametrize("over,word", [
@@ -115,3 +115,32 @@ def test_python_wrapper_rejects_shapes_before_it_needs_a_device():
         metrics.eval_metrics_u8(pred, torch.zeros(2, 8, 8, 3), mask=torch.zeros(2, 8, 8, 3))
     with pytest.raises(ValueError):
         metrics.eval_metrics_u8(pred, torch.zeros(2, 8, 8, 4), mask=torch.zeros(2, 8))
+
+
+def test_retired_entries_are_gone():
+    """ABI v17: the uint8-moments entry and the 121-tap SSIM pair are neither declared nor bound nor exported."""
+    import os
+    from splatformer_amd import _lib as L
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sfx.h")).read()
+    lib = _lib()
+    for name in ("sfx_ssim", "sfx_ssim_workspace_bytes", "sfx_image_stats_u8"):
+        assert name not in L.SIGNATURES
+        assert name + "(" not in header and name + " " not in header
+        assert not hasattr(lib, name)
+    assert lib.sfx_abi_version() == 17
+
+
+def test_thin_callers_reject_shapes_before_they_need_a_device():
+    from splatformer_amd import metrics
+    rgb, rgba, flat = torch.zeros(2, 8, 8, 3), torch.zeros(2, 8, 8, 4), torch.zeros(2, 192)
+    for a, b in ((rgba, rgba), (flat, flat), (rgb, rgba), (rgb, torch.zeros(2, 8, 9, 3)), (rgb[0], rgb[0])):
+        with pytest.raises(ValueError):
+            metrics.psnr_u8(a, b)
+        with pytest.raises(ValueError):
+            metrics.image_stats_u8(a, b)
+        with pytest.raises(ValueError):
+            metrics.ssim(a, b, quantize_u8=True)
+    with pytest.raises(ValueError):
+        metrics.ssim(rgb, rgba)
+    with pytest.raises(ValueError):
+        metrics.ssim(rgb[0], rgb[0])

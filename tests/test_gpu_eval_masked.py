@@ -122,14 +122,17 @@ def test_ssim_matches_float64_reference(device, shape, kind):
 
 @pytest.mark.parametrize("shape", SHAPES, ids=[f"{s[0]}x{s[1]}x{s[2]}" for s in SHAPES])
 def test_unmasked_agrees_with_the_existing_kernels(device, shape):
+    """An RGB target without a mask: the integer moments torch forms on the CPU, the float64 SSIM, and the same bits
+    as the RGBA form with an all-ones mask and as the thin callers psnr_u8 / image_stats_u8 / ssim(quantize_u8)."""
     c = case(shape, "ones")
     pred, gt3 = c["pred"].to(device), c["gt3"].to(device)
     got = metrics.eval_metrics_u8(pred, gt3)
+    assert torch.equal(got["sums"].cpu(), c["sums"]) and torch.equal(got["maxes"].cpu(), c["maxes"])
+    assert float((got["ssim"].cpu().double() - ssim64(shape, "ones")).abs().max()) <= 2e-6
+    assert torch.equal(got["psnr"], metrics.psnr_u8(pred, gt3))
     sums, maxes = metrics.image_stats_u8(pred, gt3)
     assert torch.equal(got["sums"], sums) and torch.equal(got["maxes"], maxes)
-    old = metrics.ssim(pred, gt3, quantize_u8=True)
-    assert float((got["ssim"] - old).abs().max()) <= 2e-6
-    assert torch.equal(got["psnr"], metrics.psnr_u8(pred, gt3))
+    assert torch.equal(got["ssim"], metrics.ssim(pred, gt3, quantize_u8=True))
     ones = run(shape, "ones", str(device))  # the same target as RGBA with an all-ones mask
     assert torch.equal(ones["sums"], got["sums"].cpu()) and torch.equal(ones["ssim"], got["ssim"].cpu())
 
@@ -151,12 +154,35 @@ def test_in_place_mask_equals_separate_mask_and_calls_repeat(device, shape, kind
 
 
 def test_clamp_pred_off_saturates_like_the_existing_kernel(device):
-    """clamp_pred=False leaves values above 1 to the uint8 saturation, as sfx_image_stats_u8 does."""
-    c = case((2, 17, 33), "ones")
-    pred, gt3 = c["pred"].to(device), c["gt3"].to(device)
-    got = metrics.eval_metrics_u8(pred, gt3, clamp_pred=False)
-    sums, maxes = metrics.image_stats_u8(pred, gt3, clamp_pred=False)
-    assert torch.equal(got["sums"], sums) and torch.equal(got["maxes"], maxes)
+    """clamp_pred=False leaves values above 1 to the truncation (below 256 / 255) and the uint8 saturation (above).
+    Without a mask the clamp cannot show in the moments (a value above 1 quantises to 255 either way), so each form
+    is held to what torch forms on the CPU from the same quantisation, and the two agree; under a mask the clamp
+    comes before the multiply (p = 1.2, m = 0.5: 153 unclamped, 127 clamped), and the two sets of moments differ."""
+    c = case((2, 17, 33), "random")
+    pred = c["pred"].clone()
+    pred[:, ::3, ::2] *= 1.3  # values in (1, 256 / 255) and well above: up to 1.02 * 1.3 * 1.2
+    gt3, ones = c["gt3"], torch.ones_like(c["mask"])
+    assert int((pred > 256 / 255).sum()) > 100 and int(((pred > 1) & (pred * 255 < 256)).sum()) > 0
+
+    def moments(p, m):  # saturating, as the kernel documents: torch's own uint8 conversion wraps above 255
+        a = ((p * m[..., None]) * 255).to(torch.int64).clamp(0, 255).reshape(2, -1)
+        b = c["gu"].to(torch.int64).reshape(2, -1)
+        return (torch.stack([(a * a).sum(1), (b * b).sum(1), (a * b).sum(1)], 1),
+                torch.stack([a.max(1).values, b.max(1).values], 1).to(torch.int32))
+
+    assert not torch.equal(moments(pred, c["mask"])[0], moments(pred.clamp(max=1.0), c["mask"])[0])
+    assert torch.equal(moments(pred, ones)[0], moments(pred.clamp(max=1.0), ones)[0])
+    on_dev = pred.to(device), gt3.to(device)
+    for clamp in (False, True):
+        p = pred.clamp(max=1.0) if clamp else pred
+        got = metrics.eval_metrics_u8(*on_dev, clamp_pred=clamp)  # an RGB target, no mask
+        sums, maxes = moments(p, ones)
+        assert torch.equal(got["sums"].cpu(), sums) and torch.equal(got["maxes"].cpu(), maxes), clamp
+        s2, m2 = metrics.image_stats_u8(*on_dev, clamp_pred=clamp)
+        assert torch.equal(got["sums"], s2) and torch.equal(got["maxes"], m2)
+        got = metrics.eval_metrics_u8(*on_dev, mask=c["mask"].to(device), clamp_pred=clamp)
+        sums, maxes = moments(p, c["mask"])
+        assert torch.equal(got["sums"].cpu(), sums) and torch.equal(got["maxes"].cpu(), maxes), clamp
 
 
 def test_empty_batch(device):
@@ -221,3 +247,24 @@ def test_evaluate_scenes_on_real_style_targets(device, tmp_path):
     assert inp == results and sorted(both) == ["0", "1"]
     assert refined["num_images"] == 6
     assert all(v == v and abs(v) != float("inf") for v in (refined["psnr"], refined["ssim"]))
+
+
+def test_evaluate_scenes_scores_rgb_and_all_ones_rgba_alike(device):
+    """Two scenes with the same pixels, one scored against an RGB target and one against that target as RGBA with an
+    all-ones mask: one path, so the per-image records are equal as floats."""
+    from splatformer_amd.evaluate import evaluate_scenes
+    from splatformer_amd.gs_render import rasterize_gaussians_to_multiimgs
+    from splatformer_amd.scenes import make_cameras, make_scene, to_device
+    scene = to_device(make_scene(2000, sh_degree=1, seed=3), device)
+    cams = to_device(make_cameras(40, 33, n_views=2), device)
+    with torch.no_grad():
+        rgbs, _ = rasterize_gaussians_to_multiimgs(scene, cams)
+    render = torch.stack(rgbs, 0).cpu()
+    rgb = (render + 0.03 * torch.rand(render.shape, generator=torch.Generator().manual_seed(5))).clamp(0, 1)
+    targets = [rgb.to(device), torch.cat([rgb, torch.ones_like(rgb[..., :1])], -1).to(device)]
+    results = {}
+    evaluate_scenes(None, [scene, scene], [cams, cams], lambda i: targets[i], device, evaluate_input=True,
+                    results=results)
+    assert results["0"] == results["1"]
+    assert len(results["0"]["psnr"]) == 2 and all(v == v and v < 100 for v in results["0"]["psnr"])
+    assert all(0 < v < 1 for v in results["0"]["ssim"])

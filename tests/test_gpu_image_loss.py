@@ -6,7 +6,7 @@ each direction with C = 1, several tiles and views, and 64 x 64 x 3.  Inputs (te
 noise, indep and flat (white background, the ill-conditioned case).
 
 Bars.  The SSIM term: 2e-6 absolute against the values captured from the reference (tests/golden/metrics.npz), the
-bar sfx_ssim is held to; on flat inputs no further from fp64 than 4x the oracle's own fp32 evaluation + 1e-7.  The
+bar metrics.ssim is held to; on flat inputs no further from fp64 than 4x the oracle's own fp32 evaluation + 1e-7.  The
 L1 and mse terms: 1e-6 relative to fp64.  The gradient: with e_hip the relative L2 of d_pred to the oracle's fp64
 autograd and e_ref32 that of the oracle's fp32 autograd on the same inputs, e_hip <= 4 e_ref32 + 1e-7, where
 e_ref32 < 1e-3 (it measures 1.5e-7 .. 3.4e-6 on noise / indep and 7e-6 .. 2e-4 on flat; a halo, padding or tap

@@ -1,4 +1,5 @@
-"""HIP uint8 PSNR (sfx_image_stats_u8) vs the oracle restatement of train.py:104-113 + utils/metrics.py.
+"""HIP uint8 PSNR and SSIM (metrics.psnr_u8 / ssim, thin callers of sfx_eval_metrics_u8 and sfx_image_loss) vs the
+oracle restatement of train.py:104-113 + utils/metrics.py.
 
 Tolerance: |dPSNR| <= 1e-4 dB (BASELINE.json north_star); the HIP side is exact integer moments, the
 oracle a float32 mean, so the difference is the oracle's rounding."""
@@ -69,7 +70,7 @@ def test_evaluate_scenes_single_rank(device):
 
 
 def test_ssim_matches_reference_golden(device):
-    """sfx_ssim vs the outputs of the reference's own utils/metrics.py ssim (tests/golden/metrics.npz) and the
+    """metrics.ssim vs the outputs of the reference's own utils/metrics.py ssim (tests/golden/metrics.npz) and the
     oracle on a render-sized batch (HWC layout as rendered; tolerance 2e-6 absolute on an SSIM in [-1, 1])."""
     import os
     import numpy as np
@@ -86,3 +87,37 @@ def test_ssim_matches_reference_golden(device):
     ref = metrics_ref.ssim(x.permute(0, 3, 1, 2), y.permute(0, 3, 1, 2), 11, size_average=False)
     got = metrics.ssim(x.to(device), y.to(device)).cpu()
     assert (got - ref).abs().max() < 2e-6
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 1, 1), (2, 4, 3, 1), (1, 17, 33, 4), (2, 16, 32, 2)])
+def test_ssim_unquantised_small_shapes(device, shape):
+    """One pixel, an image smaller than the window radius, one pixel past a 32 x 16 tile in both directions with
+    C = 4, exactly one tile: against the oracle in float64, 2e-6 absolute."""
+    from oracle import metrics_ref
+    g = torch.Generator().manual_seed(sum(shape))
+    x = torch.rand(shape, generator=g)
+    y = (x + 0.05 * torch.randn(shape, generator=g)).clamp(0, 1)
+    ref = metrics_ref.ssim(x.permute(0, 3, 1, 2).double(), y.permute(0, 3, 1, 2).double(), 11, size_average=False)
+    got = metrics.ssim(x.to(device), y.to(device)).cpu()
+    err = float((got.double() - ref).abs().max())
+    print(f"ssim {shape}: max |hip - ref64| = {err:.3e}")
+    assert got.dtype == torch.float32 and got.shape == (shape[0],)
+    assert err <= 2e-6
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 1, 3), (2, 17, 33, 3), (1, 5, 70, 3)])
+def test_ssim_quantised_clamps_img1_only(device, shape):
+    """quantize_u8: the uint8 images / 255 with img1 alone clamped to <= 1, some prediction values above 1; against
+    the oracle in float64 on the same quantisation, 2e-6 absolute."""
+    from oracle import metrics_ref
+    g = torch.Generator().manual_seed(sum(shape))
+    y = torch.rand(shape, generator=g)
+    x = (y + 0.05 * torch.randn(shape, generator=g)).clamp_min(0) * 1.05
+    x.view(-1)[0] = 1.2
+    q = lambda t: (t * 255).to(torch.uint8).float().div(255).permute(0, 3, 1, 2).double()  # noqa: E731
+    ref = metrics_ref.ssim(q(x.clamp(max=1)), q(y), 11, size_average=False)
+    got = metrics.ssim(x.to(device), y.to(device), quantize_u8=True).cpu()
+    err = float((got.double() - ref).abs().max())
+    print(f"ssim u8 {shape}: max |hip - ref64| = {err:.3e}")
+    assert got.dtype == torch.float32 and got.shape == (shape[0],)
+    assert err <= 2e-6

@@ -168,7 +168,7 @@ def test_new_entry_points_validate_on_the_host():
     import ctypes
     from splatformer_amd import _lib
     lib = _lib.load()
-    assert lib.sfx_abi_version() == 16
+    assert lib.sfx_abi_version() == 17
     I4, F4 = ctypes.c_int * 4, ctypes.c_float * 4
     buf = ctypes.create_string_buffer(4096)
     p = (ctypes.addressof(buf) + 15) // 16 * 16

@@ -119,7 +119,7 @@ def test_entries_declared_and_abi_unchanged():
     for name in ("sfx_image_loss", "sfx_image_loss_workspace_bytes"):
         assert hasattr(lib, name) and name in L.SIGNATURES
     assert len(L.SIGNATURES["sfx_image_loss"]) == 15
-    assert lib.sfx_abi_version() == 16
+    assert lib.sfx_abi_version() == 17
 
 
 @pytest.mark.parametrize("kw,word", [

@@ -194,7 +194,7 @@ def test_entries_declared_sizes_and_abi_unchanged():
                  "sfx_conv3x3", "sfx_maxpool2x2", "sfx_maxpool2x2_bwd", "sfx_lpips_input", "sfx_lpips_input_bwd",
                  "sfx_tap_normalize", "sfx_tap_dist_workspace_bytes", "sfx_tap_dist", "sfx_tap_dist_bwd"):
         assert hasattr(lib, name) and name in B.SIGNATURES
-    assert lib.sfx_abi_version() == 16
+    assert lib.sfx_abi_version() == 17
     assert lib.sfx_conv3x3_pack_bytes(64, 128) == 64 * 128 * 36 + 128 * 4   # fp16 h + l per weight, row scales
     assert lib.sfx_conv3x3_pack_bytes(3, 64) == 3 * 64 * 36                  # fp32, VALU route
     assert lib.sfx_conv3x3_pack_bytes(0, 64) == 0

@@ -20,7 +20,7 @@ def test_entries_exported_and_bound():
         assert name in _lib.SIGNATURES
     assert len(_lib.SIGNATURES["sfx_rasterize_fwd_nd"]) == 6 + len(FWD_ARGS)
     assert len(_lib.SIGNATURES["sfx_rasterize_bwd_nd"]) == 6 + len(BWD_ARGS)
-    assert lib.sfx_abi_version() == 16  # additive: the ABI number did not move
+    assert lib.sfx_abi_version() == 17
 
 
 @pytest.mark.parametrize("channels", [0, 33, -1])

@@ -23,7 +23,7 @@ def test_pinned_signatures():
     for name in (RAST, PREP):
         assert getattr(lib, name).argtypes == mod.SIGNATURES[name]
         assert getattr(lib, name).restype is ctypes.c_int
-    assert lib.sfx_abi_version() == 16  # additive: the ABI number did not move
+    assert lib.sfx_abi_version() == 17
 
 
 def _rast(views=2, tx=2, ty=2, bw=16, h=32, w=32, bufs=None):

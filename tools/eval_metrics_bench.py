@@ -1,10 +1,11 @@
-"""Time metrics.eval_metrics_u8 (one fused kernel) against the calls it replaces, on one GPU.
+"""Time the two image-quality kernels on one GPU: metrics.eval_stats_u8 (sfx_eval_metrics_u8) on an RGBA and on an
+RGB target, and losses.image_loss_and_grad (sfx_image_loss, forward + derivative) on the RGB target.
 
-Masked case (RGBA target): the composed sequence is what evaluation had to run for the same result before the fused
-kernel: slice copy of gt[..., :3], pred * mask, image_stats_u8, ssim(quantize_u8=True).  Unmasked case (RGB target):
-image_stats_u8 + ssim(quantize_u8=True) alone.  The two sides alternate inside one process; times are device
-events around `--reps` back-to-back calls, median of `--rounds` rounds.  Bytes are the least each side has to
-move, computed from the shapes (whole pixels of an RGBA target count 16 bytes: the lines are fetched whole).
+Times are device events around `--reps` back-to-back calls, median of `--rounds` rounds with the sides alternating
+inside the process.  To compare two builds of the library, run this once per build (SFX_LIB, --label) in one
+session, alternating the builds.  Bytes are the least each side has to move, computed from the shapes (whole pixels
+of an RGBA target count 16 bytes: the lines are fetched whole; the loss reads pred and gt twice and writes and reads
+three fp32 maps and d_pred).
 
     python tools/eval_metrics_bench.py --views 9 --size 800
 """
@@ -17,7 +18,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from splatformer_amd import metrics  # noqa: E402
+from splatformer_amd import losses, metrics  # noqa: E402
 
 
 def timed(fn, reps):
@@ -36,6 +37,7 @@ def main():
     ap.add_argument("--size", type=int, default=800)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--label", default="in-tree", help="name of the library build in the record")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_metrics_bench needs a GPU")
@@ -51,30 +53,11 @@ def main():
     rgb = gt.to(dev)
     pred = pred.to(dev)
 
-    def composed_masked():
-        gt3 = rgba[..., :3].contiguous()
-        pm = pred * rgba[..., 3:]
-        return metrics.image_stats_u8(pm, gt3, clamp_pred=False), metrics.ssim(pm, gt3, quantize_u8=True)
-
-    parts = {
-        "slice_copy": lambda: rgba[..., :3].contiguous(),
-        "pred_times_mask": lambda: pred * rgba[..., 3:],
-        "image_stats_u8": lambda: metrics.image_stats_u8(pred, rgb, clamp_pred=False),
-        "ssim_quantized": lambda: metrics.ssim(pred, rgb, quantize_u8=True),
-    }
-    sides = {
+    fns = {
         "masked_fused": lambda: metrics.eval_stats_u8(pred, rgba, clamp_pred=False),
-        "masked_composed": composed_masked,
         "rgb_fused": lambda: metrics.eval_stats_u8(pred, rgb, clamp_pred=False),
-        "rgb_composed": lambda: (parts["image_stats_u8"](), parts["ssim_quantized"]()),
+        "image_loss_grad": lambda: losses.image_loss_and_grad(pred, rgb, 0.8, 0.2),
     }
-    # the two sides compute the same thing at this size
-    f = metrics.eval_metrics_u8(pred, rgba, clamp_pred=False)
-    (s, mx), ss = composed_masked()
-    assert torch.equal(f["sums"], s) and torch.equal(f["maxes"], mx)
-    ssim_diff = float((f["ssim"] - ss).abs().max())
-
-    fns = {**sides, **parts}
     for fn in fns.values():  # warm every shape
         for _ in range(3):
             fn()
@@ -85,14 +68,12 @@ def main():
             times[k].append(timed(fn, args.reps))
     px = V * H * W
     out = {
+        "library": args.label,
         "views": V, "height": H, "width": W, "reps": args.reps, "rounds": args.rounds,
         "us_median": {k: round(statistics.median(v), 2) for k, v in times.items()},
         "us_min_max": {k: [round(min(v), 2), round(max(v), 2)] for k, v in times.items()},
-        "ssim_max_abs_diff_fused_vs_composed": ssim_diff,
-        # least bytes: fused reads pred (12 B/px) and the target once; composed: slice (16 in, 12 out), multiply
-        # (12 + 16 in, 12 out), stats (24 in), ssim (24 in)
-        "min_bytes": {"masked_fused": 28 * px, "masked_composed": (28 + 40 + 24 + 24) * px,
-                      "rgb_fused": 24 * px, "rgb_composed": 48 * px},
+        "us_rounds": {k: [round(t, 2) for t in v] for k, v in times.items()},
+        "min_bytes": {"masked_fused": 28 * px, "rgb_fused": 24 * px, "image_loss_grad": (24 + 36 + 36 + 24 + 12) * px},
     }
     print(json.dumps(out))
 
